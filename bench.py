@@ -19,7 +19,14 @@ Default workload = north_star's headline problem, the size of BASELINE.json conf
 15 kb bins (hg38, ~5 % of bins masked) x 500 reference samples, refsize 300 -- it fits one
 GPU; with --gpus N the same problem is row-sharded (strong scaling).  Inputs are resident in
 HBM when the timed region starts.  value = candidate bin pairs evaluated per second over the
-whole job ("bins x refs / s").  A secondary block carries configs[2] (100 samples).
+whole job ("bins x refs / s").
+
+A plain run sets up, warms up, times the --steps steps and prints the line: metric, value, unit,
+ms_per_step (one timed step), dtype, config.  --dump-outputs DIR also writes what the last timed step
+computed (see dump_outputs).  --full adds everything else, all outside the timed steps: roofline and
+per-kernel times (three extra untimed steps), the collective log of N > 1, HBM figures, the oracle
+check, the secondary block with configs[2] (100 samples), RCCL with one rank, configs 5 and 100 kb, the
+preparation pipeline, the CLI end to end and the CPU baselines (the --no-* options drop single blocks).
 """
 import argparse
 import hashlib
@@ -275,6 +282,7 @@ class Workload:
         self.fb_rows = []
         self.n_segments = 0
         self.last = None                             # (idx, dist) of the last step's A pass, for verify_rows
+        self.last_segments = None                    # the predict's segments of the last step
         self.stats_A = None
 
     def step(self, record):
@@ -341,6 +349,7 @@ class Workload:
         t0 = time.perf_counter()
         res = wd.predict_full_dev(self.backend, ref["A"], ref["F"], self.d_xA, self.d_xG, self.rem, self.pt)
         self.n_segments = len(res)
+        self.last_segments = res
         if record:
             self.ms["predict_full"].append(1e3 * (time.perf_counter() - t0))
             self.ms["normalize"].append(ctx.kernel_ms("aut:normalize") + max(0.0, ctx.kernel_ms("normalize")))
@@ -729,6 +738,54 @@ def rccl_world1_block(w, torch, dev):
     return out
 
 
+DUMP_PASS_BYTES = {"A": 24 << 20, "F": 8 << 20, "M": 8 << 20}   # --dump-outputs: 40 MiB of tables
+DUMP_BIN_BYTES = 16 << 20                                          # + the predict's per-bin values
+
+
+def _sample_rows(n, cap, seed):
+    """A fixed, seeded, sorted sample of cap of range(n) (all of it when n <= cap)."""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False)).astype(np.int64)
+
+
+def dump_outputs(w, outdir):
+    """--dump-outputs: what a caller of the timed path received from the LAST timed step, as float64
+    DIR/<name>.npy (indices are exact in float64; 56 MiB at most):
+      <pass>_indexes / _distances / _null_ratios  the reference tables of the A, F and M passes on a
+                 fixed, seeded sample of their searched rows (A: all rows, F / M: the gonosomal rows),
+                 <pass>_rows = which rows;
+      predict_ratio / _z / _weight  the predict's per-bin values after the merge and post-processing
+                 (predict_bins = which bins, when they had to be sampled);
+      predict_segments  its segments [chr, start, end, z, ratio]."""
+    torch = w.torch
+    torch.cuda.synchronize()
+    arrays = {}
+    for seed, tag in enumerate(("A", "F", "M")):
+        t = w.last_ref[tag]
+        B = int(w.P[tag]["B"])
+        lo = 0 if tag == "A" else int(w.P[tag]["cum"][21])
+        row_bytes = 8 * (1 + 2 * int(t["idx"].shape[1]) + int(t["nr"].shape[1]))
+        rows = lo + _sample_rows(B - lo, DUMP_PASS_BYTES[tag] // row_bytes, seed)
+        sel = torch.from_numpy(rows).to(t["idx"].device)
+        arrays[tag + "_rows"] = rows
+        for name, key in (("indexes", "idx"), ("distances", "dist"), ("null_ratios", "nr")):
+            arrays["{}_{}".format(tag, name)] = t[key].index_select(0, sel).cpu().numpy()
+    per_bin = w.backend._predict_full_bufs["out"][:, 0, :]          # [3][n_bins]: r, z, w of the sample
+    bins = _sample_rows(per_bin.shape[1], DUMP_BIN_BYTES // 32, 3)
+    if len(bins) < per_bin.shape[1]:
+        arrays["predict_bins"] = bins
+    per_bin = per_bin.index_select(1, torch.from_numpy(bins).to(per_bin.device)).cpu().numpy()
+    for j, name in enumerate(("ratio", "z", "weight")):
+        arrays["predict_" + name] = per_bin[j]
+    arrays["predict_segments"] = np.array([[float(v) for v in r_] for r_ in w.last_segments],
+                                          dtype=np.float64).reshape(-1, 5)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def run_steps(w, steps, warmup, spinup, barrier):
     # Untimed spin-up (setup, not one of the contract's warm-up steps; reported in config): the
     # first process on an idle box otherwise measures the clock ramp.  A FIXED number of steps:
@@ -753,6 +810,11 @@ def main():
     ap.add_argument("--binsize", type=int, default=15000)
     ap.add_argument("--samples", type=int, default=500)
     ap.add_argument("--refsize", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline "
+                         "figure (roofline, verification, other configs, CLI, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the S=100 block")
     ap.add_argument("--no-verify", action="store_true", help="skip the post-run oracle check")
@@ -813,6 +875,63 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
+
+    out = {
+        "metric": "newref+predict throughput @{}kb bins (bins x refs per second)".format(
+            args.binsize // 1000),
+        "value": (world if args.replicas else 1) * w.pairs_total / (ms_per_step * 1e-3),
+        "unit": "bin-pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak" if args.replicas else "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "newref {} kb bins, {} samples, refsize={}: A pass (B={} masked autosomal "
+                               "bins x S={}) + F pass ({} chrX rows x S={}) + M pass ({} chrX/Y rows x "
+                               "S={}), each search + null ratios + gather of the reference; + predict of "
+                               "1 sample (cut-off, weights, 3 normalisation passes for autosomes and "
+                               "gonosomes, merge, post-processing, CBS of 23 chromosomes, segment z).  The step "
+                               "starts from the prepared matrices resident in HBM: masks, depth normalisation, "
+                               "PCA correction + distance filter (newref_tools.py:77-147, newref_control.py:38-58) "
+                               "and all file I/O are OUTSIDE it -- their device time is `prep_pipeline`, the "
+                               "whole CLI `e2e_cli`".format(
+                                   args.binsize // 1000, w.S, w.k,
+                                   w.B, w.S, w.P["F"]["B"] - int(w.P["F"]["cum"][21]), w.P["F"]["S"],
+                                   w.P["M"]["B"] - int(w.P["M"]["cum"][21]), w.P["M"]["S"]),
+                   "bins": int(w.B), "samples": int(w.S), "refsize": int(w.k),
+                   "pairs": w.pairs_total, "bin_samples_per_s": w.B * w.S / (ms_per_step * 1e-3),
+                   "spinup_steps_untimed": SPINUP_STEPS, "predict_segments": w.n_segments,
+                   "precision": "indices and distances bit-identical to the reference's fp64 path; the "
+                                "fp16 MFMA product is only a rigorously bounded pre-filter, every "
+                                "kept pair is re-evaluated in sequential fp64",
+                   "partition": "target rows x{} (A: _get_part over all rows; F / M: over their gonosomal "
+                                "rows): per pass one all-gather(X) for the search and one all-gather of "
+                                "the finished row blocks; predict replicated".format(world)
+                                if not args.replicas else
+                                "{} independent replicas (one whole reference + predict per rank), no "
+                                "collective on the data path".format(world)},
+    }
+    if args.full:
+        full_report(args, w, out, torch, dist, dev, dev_index, rank, world, backend_name, barrier)
+    if world > 1:
+        barrier()                   # (rank 0 verifies after the timed region: nobody tears the group down under it)
+        dist.destroy_process_group()
+    sys.stdout.flush()
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)           # C stdio buffers (RCCL's banner) -> stderr, not after the JSON
+    except Exception:
+        pass
+    os.dup2(real_stdout, 1)
+    os.close(real_stdout)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def full_report(args, w, out, torch, dist, dev, dev_index, rank, world, backend_name, barrier):
+    """--full: everything beyond the headline figure, after the timed steps (and after --dump-outputs
+    has written their outputs): each block below adds its key(s) to `out`."""
     ranks_info = None
     if world > 1 and not args.replicas and not args.debug_flags:
         # one extra untimed step with the collectives logged (events around each blocking collective):
@@ -887,42 +1006,7 @@ def main():
                 return
     if screen_ms >= 0:
         add_traffic(roofline, w.S, w.B)
-
-    out = {
-        "metric": "newref+predict throughput @{}kb bins (bins x refs per second)".format(
-            args.binsize // 1000),
-        "value": (world if args.replicas else 1) * w.pairs_total / (ms_per_step * 1e-3),
-        "unit": "bin-pairs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak" if args.replicas else "strong",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "newref {} kb bins, {} samples, refsize={}: A pass (B={} masked autosomal "
-                               "bins x S={}) + F pass ({} chrX rows x S={}) + M pass ({} chrX/Y rows x "
-                               "S={}), each search + null ratios + gather of the reference; + predict of "
-                               "1 sample (cut-off, weights, 3 normalisation passes for autosomes and "
-                               "gonosomes, merge, post-processing, CBS of 23 chromosomes, segment z).  The step "
-                               "starts from the prepared matrices resident in HBM: masks, depth normalisation, "
-                               "PCA correction + distance filter (newref_tools.py:77-147, newref_control.py:38-58) "
-                               "and all file I/O are OUTSIDE it -- their device time is `prep_pipeline`, the "
-                               "whole CLI `e2e_cli`".format(
-                                   args.binsize // 1000, w.S, w.k,
-                                   w.B, w.S, w.P["F"]["B"] - int(w.P["F"]["cum"][21]), w.P["F"]["S"],
-                                   w.P["M"]["B"] - int(w.P["M"]["cum"][21]), w.P["M"]["S"]),
-                   "bins": int(w.B), "samples": int(w.S), "refsize": int(w.k),
-                   "pairs": w.pairs_total, "bin_samples_per_s": w.B * w.S / (ms_per_step * 1e-3),
-                   "spinup_steps_untimed": SPINUP_STEPS, "predict_segments": w.n_segments,
-                   "precision": "indices and distances bit-identical to the reference's fp64 path; the "
-                                "fp16 MFMA product is only a rigorously bounded pre-filter, every "
-                                "kept pair is re-evaluated in sequential fp64",
-                   "partition": "target rows x{} (A: _get_part over all rows; F / M: over their gonosomal "
-                                "rows): per pass one all-gather(X) for the search and one all-gather of "
-                                "the finished row blocks; predict replicated".format(world)
-                                if not args.replicas else
-                                "{} independent replicas (one whole reference + predict per rank), no "
-                                "collective on the data path".format(world)},
-        "roofline": roofline,
-    }
+    out["roofline"] = roofline
     if rank == 0 and world == 1 and not args.no_secondary and not args.debug_flags \
             and args.samples != 100:
         w2 = Workload(args, 100, torch, dev, dev_index, rank, world)
@@ -977,19 +1061,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w.Xs_host, w.cum, w.k)
         out["cpu_baseline"]["predict"] = cpu_baseline_predict(w)
-    if world > 1:
-        barrier()                   # (rank 0 verifies after the timed region: nobody tears the group down under it)
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)           # C stdio buffers (RCCL's banner) -> stderr, not after the JSON
-    except Exception:
-        pass
-    os.dup2(real_stdout, 1)
-    os.close(real_stdout)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

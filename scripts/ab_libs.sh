@@ -2,7 +2,7 @@
 # Same-box comparison of builds of the library: wisecondorx_amd/libwcx_hip_<tag>.so for every tag given
 # (the tracked build first and last).  Prints step / sweep / refine / verification per build.
 mkdir -p gpurun_out
-B="python bench.py --steps 6 --warmup 2 --no-extras --no-secondary --no-cpu-baseline"
+B="python bench.py --full --steps 6 --warmup 2 --no-extras --no-secondary --no-cpu-baseline"
 sum() { python - "$1" <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']

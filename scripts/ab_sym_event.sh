@@ -2,7 +2,7 @@
 # Same-box A / B of two builds of libwcx_hip.so (wisecondorx_amd/libwcx_hip_old.so = the build to compare
 # against, made from an older tree): step, sweep, S = 100 block, F / M passes, 100 kb; then the sweep tests.
 mkdir -p gpurun_out
-B="python bench.py --steps 8 --warmup 3 --no-extras --no-cpu-baseline"
+B="python bench.py --full --steps 8 --warmup 3 --no-extras --no-cpu-baseline"
 sum() { python - "$1" <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']; s=d.get('secondary',{}); g=r['gonosomal_passes']

@@ -1,8 +1,9 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_nr
+R=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for r in 4 1; do
-  WCX_NR_DIRECT_RATIO=$r timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT/r$r -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-verify > $OUT/r$r.log 2>&1
+  WCX_NR_DIRECT_RATIO=$r timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT/r$r -o p -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-verify > $OUT/r$r.log 2>&1
 done
 cd $GRAFT_REPO_ROOT
 python - <<'PY'

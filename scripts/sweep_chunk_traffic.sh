@@ -2,12 +2,13 @@
 # A-pass screen: HBM-side fetch (rocprofv3 --pmc FETCH_SIZE, x2 per MI355X_MICROARCH.md) and sweep time
 # against the candidate chunk size of its launches (WCX_SCREEN_CHUNK_KB; default 8192 at K = 512).
 OUT=$GRAFT_REPO_ROOT/gpurun_out/chunk_traffic
+R=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for kb in 8192 16384 32768 65536 131072; do
   export WCX_SCREEN_CHUNK_KB=$kb
-  timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c$kb -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-verify > $OUT/c$kb.log 2>&1
-  timeout 200 python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-verify > $OUT/b$kb.json 2>/dev/null
+  timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c$kb -o p -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-verify > $OUT/c$kb.log 2>&1
+  timeout 200 python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-verify > $OUT/b$kb.json 2>/dev/null
 done
 cd $GRAFT_REPO_ROOT
 python - <<'PY'

@@ -1,6 +1,6 @@
 for s in 0 2 3 4 6 8; do
   if [ $s = 0 ]; then unset WCX_SCREEN_SEGMENTS; else export WCX_SCREEN_SEGMENTS=$s; fi
-  python bench.py --binsize 100000 --samples 100 --steps 30 --warmup 5 --no-secondary --no-extras --no-cpu-baseline > /tmp/o.json 2>/dev/null
+  python bench.py --full --binsize 100000 --samples 100 --steps 30 --warmup 5 --no-secondary --no-extras --no-cpu-baseline > /tmp/o.json 2>/dev/null
   python - $s <<'PY'
 import json,sys
 d=json.loads(open('/tmp/o.json').read().strip().splitlines()[-1])

@@ -4,12 +4,13 @@
 # workgroups running at any time stream the same one or two chunks: a chunk that fits an XCD's 4 MB L2 is
 # fetched once per XCD, a larger one cycles through it).
 OUT=$GRAFT_REPO_ROOT/gpurun_out/sym_chunk_traffic
+R=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for kb in 1536 2048 3072 4096 8192; do
   export WCX_SYM_CHUNK_KB=$kb
   timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c$kb -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-verify --no-extras --concurrent-passes 0 > $OUT/c$kb.log 2>&1
-  timeout 200 python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-verify --no-extras > $OUT/b$kb.json 2>/dev/null
+  timeout 200 python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-verify --no-extras > $OUT/b$kb.json 2>/dev/null
 done
 cd $GRAFT_REPO_ROOT
 python - <<'PY'

@@ -13,6 +13,7 @@ Shims:
   * CBS needs R/DNAcopy (absent) -> exec_R patched with hand-made segments.
 """
 import argparse
+import glob
 import os
 import random
 import sys
@@ -50,10 +51,29 @@ ref_pt.project_pc = _project_pc_le14
 ref_pc.project_pc = _project_pc_le14
 
 
+PART_LIMIT = 1000000       # bytes: an archive that would be larger goes out in parts
+
+
 def save(name, **kw):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **kw)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    """<name>, split into <stem>.npz + <stem>_part2.npz ... when one archive would be larger than
+    PART_LIMIT (the arrays dealt out largest first, each to the part holding the fewest bytes);
+    tests/conftest.py load_golden() joins the parts again."""
+    stem = os.path.join(HERE, name[:-len(".npz")])
+    for old in glob.glob(stem + "_part*.npz"):
+        os.remove(old)
+    for n in range(1, len(kw) + 1):
+        parts = [{} for _ in range(n)]
+        for k in sorted(kw, key=lambda k_: -np.asarray(kw[k_]).nbytes):
+            min(parts, key=lambda p: sum(np.asarray(v).nbytes for v in p.values()))[k] = kw[k]
+        paths = [stem + ".npz"] + ["{}_part{}.npz".format(stem, i + 1) for i in range(1, n)]
+        for path, p in zip(paths, parts):
+            np.savez_compressed(path, **p)
+        if all(os.path.getsize(path) <= PART_LIMIT for path in paths):
+            break
+        for path in paths[1:]:
+            os.remove(path)
+    for path in paths:
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
 # --------------------------------------------------------------------------- newref search

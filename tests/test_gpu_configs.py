@@ -5,12 +5,11 @@
 All through the C-ABI.  Bit-exact for indices / distances / bin counts, 1e-9 for z / ratios
 (north_star: 1e-5)."""
 import argparse
-import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import load_golden
 from oracle import c_oracle as CO
 from oracle import wcx_oracle as O
 
@@ -29,7 +28,7 @@ def test_config1_predict_1mb_vs_50_sample_reference():
     (SHA-256 of the full tables), then pt.normalize reproduces its r / z / w / n / medians."""
     from test_oracle_golden import config1_reference, config1_sample
     from wisecondorx_amd import newref_tools as nt, predict_tools as pt
-    g = np.load(os.path.join(GOLDEN, "config1.npz"), allow_pickle=False)
+    g = load_golden("config1")
 
     def search(X, mb, cum, k):
         return nt.get_ref_for_rows(X, cum, k, 0, cum[-1])

@@ -108,7 +108,7 @@ def test_bench_two_ranks_smoke(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", n,
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", n, "--steps", "2", "--warmup", "1", "--binsize", "100000", "--samples", "40",
-           "--refsize", "100"] + (["--replicas"] if mode == "replicas" else [])
+           "--refsize", "100", "--full"] + (["--replicas"] if mode == "replicas" else [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -204,9 +204,8 @@ def config1_sample(g, gender):
 
 
 def test_config1_predict_1mb_vs_50_sample_reference():
-    import os
-    from conftest import GOLDEN
-    g = np.load(os.path.join(GOLDEN, "config1.npz"), allow_pickle=False)
+    from conftest import load_golden
+    g = load_golden("config1")
 
     def search(X, mb, cum, k):
         i, d, _ = O.get_reference(X, mb, cum, k, 1, 1, [0])
