@@ -1044,81 +1044,444 @@ bool wcx_screen_supported(int64_t B, int S, int k) {
   return S <= SMAX_SCREEN && k <= KMAX_SCREEN && B >= 2048;
 }
 
-static int env_int(const char *name, int dflt);
+// ctx->debug_flags as the search reads them (diagnostics, wcx_debug_flags)
+constexpr int DBG_SWEEP = 3;         // bits the sweep kernels test: 1 = no appends, 2 = matrix pipe + staging only
+constexpr int DBG_PROF = 4;          // the profiling instantiation of k_screen (NK = 7, 32)
+constexpr int DBG_ABLATIONS = 123;   // any of these: the rows stay unfinished (no hub verdict)
+constexpr int DBG_TRIG_SHIFT = 8;    // bits 8 and up: the main pass's cut trigger instead of LIM
+
 // Row pitch of the row-major copy Xr the refine gathers from, in doubles: rows start on 128-byte
 // lines (16 doubles), so that a 16-sample chunk of a candidate row is ONE aligned cache line -- with
 // a 32-byte-aligned pitch (4 000-byte rows at S = 500) every chunk straddles two lines and the L2s
-// see twice the requests.  WCX_ROW_ALIGN overrides (doubles; multiple of 4).
-static int row_pitch(int S) {
-  int a = env_int("WCX_ROW_ALIGN", 16);
-  if (a < 4 || (a & 3)) a = 4;
-  return (S + a - 1) / a * a;
-}
+// see twice the requests.
+static int row_pitch(int S) { return (S + 15) / 16 * 16; }
 
-static int env_int(const char *name, int dflt) {
+// An environment knob: unset or empty = the default, else atoi of its value
+struct Knob {
+  bool set = false;
+  int v = 0;
+  const char *str = nullptr;
+  int operator()(int dflt) const { return set ? v : dflt; }
+};
+static Knob env_knob(const char *name) {
+  Knob k;
   const char *e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
+  if (e && *e) { k.set = true; k.v = atoi(e); k.str = e; }
+  return k;
 }
 
-static int screen_dispatch(const ScreenCfg &c, const ScreenArgs &a, unsigned grid, size_t lds,
-                           hipStream_t st) {
-  int rc = wcx_screen_launch_k1(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k2(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k3(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k4(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k5(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k6(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k7(c, a, grid, lds, st);
-  if (rc < 0) rc = wcx_screen_launch_k8(c, a, grid, lds, st);
+// Every WCX_* knob of the search, read when an entry point constructs it (never cached: tests change
+// them between calls).  The default is given where a knob is used.
+struct Knobs {
+  // set by tests
+  Knob sym = env_knob("WCX_SCREEN_SYM");                // symmetric sweep: 0 never, 1 where it pays, 2 where possible
+  Knob sample = env_knob("WCX_SCREEN_SAMPLE");          // sampling rate SF of the pre-pass (outside 2 .. 64: none)
+  Knob cut_r = env_knob("WCX_SCREEN_CUT_R");            // a forced sample rank (the final cut catches unsafe ones)
+  Knob screen_hub = env_knob("WCX_SCREEN_HUB");         // 0 = no hub-count thresholds in the one-directional sweep
+  Knob segments = env_knob("WCX_SCREEN_SEGMENTS");      // candidate segments of the one-directional sweep
+  Knob sym_hub = env_knob("WCX_SYM_HUB");               // 0 = no hub-count attempt in the symmetric sweep
+  Knob sym_chunk_kb = env_knob("WCX_SYM_CHUNK_KB");     // fragment KB per chunk of the symmetric sweep
+  Knob sym_split = env_knob("WCX_SYM_SPLIT");           // > 0: work items per quad and chunk, not by the fill rule
+  Knob sym_fill = env_knob("WCX_SYM_FILL");             // work items a chunk should offer, in workgroup slots
+  Knob hub_test_fail = env_knob("WCX_HUB_TEST_FAIL");   // != 0: a hub count nobody reaches (no row gets an estimate)
+  Knob pool_ovf = env_knob("WCX_SYM_TEST_POOL_OVF");    // != 0: the sharded sweep acts as if its pool overflowed
+  // set by scripts/
+  Knob tile = env_knob("WCX_SCREEN_TILE");              // "ctg,tt,wpb,lb,ring": the sweep's configuration
+  Knob hub1_trials = env_knob("WCX_HUB1_TRIALS");       // trial thresholds per row, one-directional hub-count pass
+  Knob hub_n1 = env_knob("WCX_HUB_N1");                 // hub tiles of the moment phase
+  Knob hub_frac = env_knob("WCX_HUB_FRAC");             // the hub region is 1 / this of the rows (<= 1: no hub region)
+  Knob chunk_kb = env_knob("WCX_SCREEN_CHUNK_KB");      // fragment KB per k_screen launch
+  Knob chunk_kb_small = env_knob("WCX_SCREEN_CHUNK_KB_SMALL");   // ... when the sweep runs in segments
+  Knob segments_small = env_knob("WCX_SCREEN_SEGMENTS_SMALL");   // segments of a shard too small for the chip
+};
+
+// ---- per-shape decisions
+// One fp16 plane (its 2^-11 representation error only widens the shortlists by a few dozen
+// entries; a hi+lo three-product form was measured 35 % slower end to end).  K = 16 NK holds the
+// S data columns + 4 augmented columns (see k_screen_prep); NK is rounded up to an instantiated
+// value.
+static int screen_nk(int S) {
+  static const int nk_list[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64};
+  for (int v : nk_list)
+    if (16 * v >= S + 4) return v;
+  return 64;
+}
+
+// Kernel configuration (measured on MI355X): 128 targets per workgroup; small K:
+// 64 candidates per iteration, 3 waves per SIMD, LDS-DMA ring of 3; large K: 2 waves per SIMD
+// (the targets' fragments alone take 4 NK registers), LDS-DMA double buffer.
+// More than 508 samples (NK = 40 .. 64): the fragments of a wave's 32 targets alone take 160 .. 256
+// registers -- one wave per SIMD on the unified VGPR + AGPR file, one workgroup per CU, a double
+// buffer of 40 .. 64 KB groups in LDS.
+static ScreenCfg default_cfg(int NK) {
+  ScreenCfg c;
+  c.nk = NK; c.tt = 1; c.wpb = 4; c.prof = 0;
+  if (NK <= 8) { c.ctg = 2; c.lb = 3; c.ring = 3; }
+  else if (NK <= 32) { c.ctg = NK <= 16 ? 2 : 1; c.lb = 2; c.ring = 2; }
+  else { c.ctg = 1; c.lb = 1; c.ring = 2; }
+  return c;
+}
+
+// r = a rank in the sample that the k-th nearest of all candidates stays below with
+// overwhelming probability (mean k/SF of the k nearest fall into the sample; + 10 % for the
+// uneven share of the own chromosome, Poisson tail 1e-6 per row): the estimate admits ~r SF
+// candidates; a row whose estimate fails costs ~0.1 ms in the device-wide redo.
+// The estimate is the raw r-th sample value (a filter margin like a proven threshold's, rounds 2-4, was
+// dropped), r chosen for the rank the final cut needs below the estimate -- that of the k-th neighbour's
+// filter bound: 1.135 k entries survive the final cut at 15 kb (S = 100 and 500), allowed for with 1.18 k.
+static int sample_rank(int k, int SF, int64_t P_s, int nseg, const Knobs &kn) {
+  if (!SF) return 0;
+  // smallest r with P(Poisson(lambda) >= r) <= 1e-6 / n_seg,  lambda = 1.1 x 1.18 k / (SF n_seg)
+  const double lambda = 1.1 * 1.18 * (double)k / ((double)SF * nseg);
+  const double target = 1e-6 / nseg;
+  double term = exp(-lambda), cdf = 0.0;   // term = P(X = i)
+  int i = 0;
+  for (; i < 4 * k; ++i) {
+    if (1.0 - cdf <= target && (double)i > lambda) break;
+    cdf += term;
+    term *= lambda / (double)(i + 1);
+  }
+  int r = i + 1;
+  // the sample must hold several times r candidates and r must be well below k
+  if (r * 2 > k || P_s / nseg < 16 * (int64_t)r) r = 0;
+  // testing: a deliberately unsafe rank makes estimates fail, which the final cut must detect
+  // (rows go to the exact kernel; results stay identical)
+  const int forced = kn.cut_r(0);
+  if (forced > 0 && forced < k) r = forced;
+  return r;
+}
+
+// regroup the searched row ranges into workgroups of <= max_rows rows (same chromosome)
+static std::vector<ScreenBlock> merge_blocks(const std::vector<TopkBlock> &exact_blocks, const int64_t *chr_cum,
+                                             int n_chr, int max_rows) {
+  std::vector<ScreenBlock> out;
+  size_t i = 0;
+  while (i < exact_blocks.size()) {
+    ScreenBlock sb;
+    sb.row0 = exact_blocks[i].row0;
+    sb.nrows = exact_blocks[i].nrows;
+    sb.chr = 0;
+    for (int c = 0; c < n_chr; ++c)
+      if (chr_cum[c] == exact_blocks[i].ce && (c ? chr_cum[c - 1] : 0) == exact_blocks[i].cs) sb.chr = c;
+    sb.cs = exact_blocks[i].cs;
+    sb.ce = exact_blocks[i].ce;
+    size_t j = i + 1;
+    while (j < exact_blocks.size() && exact_blocks[j].cs == sb.cs &&
+           exact_blocks[j].row0 == sb.row0 + sb.nrows && sb.nrows + exact_blocks[j].nrows <= max_rows) {
+      sb.nrows += exact_blocks[j].nrows;
+      ++j;
+    }
+    out.push_back(sb);
+    i = j;
+  }
+  return out;
+}
+
+enum class ScreenPath { sym, exact, one_dir };
+struct ScreenPlan {
+  ScreenCfg cfg;                      // the sweep's configuration (cfg.nk = NK)
+  int hw_cus = 256, slots = 0;        // compute units; resident workgroups of cfg on all of them
+  int hub_need = 0;                   // hub candidates wanted below an estimate, as the kernels get it
+  int64_t hub_rows = 0;               // rows of the hub region asked for
+  bool hub_ok = false;                // large enough K, and the region is at most a sixth of the rows
+  ScreenPath path = ScreenPath::one_dir;
+  std::vector<ScreenBlock> blocks;    // target workgroups of the sweep
+  std::vector<ScreenBlock> hub_blocks;   // ... of the one-directional hub-count pass if cfg's differ
+  bool use_hub1 = false;              // one-directional sweep with hub-count thresholds
+  int SF = 0, n_seg = 1, cut_r = 0;   // sampling rate, candidate segments, sample rank (0: no pre-pass)
+};
+static ScreenPlan plan_shape(wcx_ctx *ctx, int64_t B, int k, const ScreenCfg &cfg, const Knobs &kn) {
+  ScreenPlan p;
+  p.cfg = cfg;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
+    p.hw_cus = prop.multiProcessorCount;
+  p.slots = p.hw_cus * (cfg.lb * 4 / cfg.wpb > 0 ? cfg.lb * 4 / cfg.wpb : 1);
+  // Hub-count thresholds: the head region of the sweep order is the hub region -- 1 / WCX_HUB_FRAC of the
+  // rows, at least 8 x the entries wanted below an estimate (1.18 k: the k-th neighbour's filter bound
+  // ranks ~1.14 k) + the 512 candidates of the moment phase (the loosest trial sits at 4 x need among what
+  // is left after the row's own chromosome is taken out).  Its size only the device knows: the host sizes
+  // everything for the bound.
+  const int need = (int)(1.18 * k) + 8;
+  p.hub_need = kn.hub_test_fail(0) ? (1 << 28) : need;   // (tests: every row ends without an estimate)
+  // (few samples: the distances are noisier and the neighbours less concentrated on the low-norm rows --
+  //  two thirds of them in the lowest 1/16 at S = 100 against 98 % at S = 500: a larger region)
+  const int frac = kn.hub_frac(cfg.nk >= 16 ? 32 : 12);
+  p.hub_rows = frac > 1 ? B / frac : 0;
+  if (p.hub_rows < 8 * (int64_t)need + 512) p.hub_rows = 8 * (int64_t)need + 512;
+  p.hub_ok = cfg.nk >= 5 && frac > 1 && p.hub_rows * 6 <= B;
+  return p;
+}
+
+// The search of the rows of exact_blocks (all rows: all_rows): which sweep, its configuration and pre-pass
+static ScreenPlan plan_search(wcx_ctx *ctx, int64_t B, int S, int k, bool all_rows, const Knobs &kn,
+                              const std::vector<TopkBlock> &exact_blocks, const int64_t *chr_cum, int n_chr) {
+  const int NK = screen_nk(S);
+  ScreenCfg cfg = default_cfg(NK);
+  cfg.prof = (ctx->debug_flags & DBG_PROF) && (NK == 7 || NK == 32) ? 1 : 0;
+  int tl[5];
+  if (kn.tile.set && sscanf(kn.tile.str, "%d,%d,%d,%d,%d", &tl[0], &tl[1], &tl[2], &tl[3], &tl[4]) == 5) {
+    cfg.ctg = tl[0]; cfg.tt = tl[1]; cfg.wpb = tl[2]; cfg.lb = tl[3]; cfg.ring = tl[4];
+  }
+  ScreenPlan p = plan_shape(ctx, B, k, cfg, kn);
+  const int TGT_WG = 32 * cfg.tt * cfg.wpb;
+  p.blocks = merge_blocks(exact_blocks, chr_cum, n_chr, TGT_WG);
+  // Sampled pre-pass: the rows b = 0 (mod SF) are swept first (own region of the sweep order).
+  // (small problems with few samples -- the reference's default 100 kb bins: 27 k rows -- are bound by
+  //  their appends like every K < 256 sweep; without estimates the lists fill to the cut trigger first:
+  //  100 kb x 100 samples, sampling 0 / 4 / 8 / 16: appends per row 1 540 / 1 230 / 1 080 / 1 075, sweep
+  //  1.61 / 1.49 / 1.44 / 1.56 ms.  K >= 256 below 32 768 rows stays without: the symmetric path it would
+  //  open is sized and tested for the larger problems.)
+  int SF = kn.sample((B >= 32768) ? 16 : ((B >= 8192 && NK < 16) ? 8 : 0));
+  if (SF < 2 || SF > 64) SF = 0;
+  const int64_t n_s = SF ? (B + SF - 1) / SF : 0;                 // rows in the sample
+  const int64_t P_s = (n_s + CT - 1) / CT * CT;                   // positions of the sample region
+  // Thresholds from COUNTS over the low-norm rows instead of the sampled pre-pass (screen_hub1.h; round 6:
+  // what round 5 gave the symmetric sweep, for row shards, gonosomal passes and K < 256).  WCX_SCREEN_HUB=0:
+  // off; an explicit sampling rate / sample rank asks for the sampled pre-pass (tests of that path).
+  const bool hub1 = kn.screen_hub(kn.sample.set || kn.cut_r.set ? 0 : 1) != 0 && p.hub_ok && cfg.wpb == 4 &&
+                    cfg.ring >= 2;
+  // Candidate segments fill the chip when a row shard has few target blocks (multi-GPU builds)
+  // and even out the last round of workgroups: work items = blocks x segments.
+  // (measured on row shards of 1/2 .. 1/8 of the 15 kb problem, profiles/r02/shard_search_*.json: with
+  // the sampled pre-pass and 2-3 resident workgroups per CU the split no longer pays -- 1 segment
+  // is as fast or faster down to 178 blocks -- so it is off unless asked for)
+  int n_seg = 1;
+  // ... except for very small shards: the gonosomal passes search ~80-100 blocks of chrX / chrY
+  // rows on 512 slots; 1 / 2 / 4 segments: F pass 7.7 / 6.8 / 6.4 ms, M pass 8.8 / 7.6 / 7.4 ms
+  // (15 kb, 250 samples each, profiles/r03)
+  // Round 6 (hub-count thresholds: the segments' lists are short, the merge cheap): as many segments as fill
+  // ONE round of workgroup slots -- F pass, 77 blocks: 4 / 5 / 6 / 8 segments = screen 1.77 / 1.65 / 1.60 /
+  // 1.95 ms; M pass, 97 blocks: 4 / 5 / 6 = 2.13 / 1.95 / 2.50 (6 x 97 > 512 slots: a second round)
+  // (with hub-count thresholds already from half a round on: 100 kb x 100, 213 blocks on 768 slots, 1 / 2 / 3
+  //  segments = sweep 1.27 / 1.02 / 0.94 ms; with the sampled pre-pass segments made that shape slower, round 5)
+  if ((int)p.blocks.size() * (hub1 ? 2 : 4) <= p.slots) {
+    int fill = p.slots / (int)p.blocks.size();
+    if (fill > 8) fill = 8;
+    n_seg = kn.segments_small(fill);
+  }
+  n_seg = kn.segments(n_seg);
+  if (n_seg < 1) n_seg = 1;
+  if (n_seg > 8) n_seg = 8;
+  p.n_seg = n_seg;
+  // All rows searched against all rows with a sampled pre-pass available: the symmetric sweep
+  // (half the matrix work; screen_sym.h).  WCX_SCREEN_SYM: 0 = never, 1 = where it pays (default),
+  // 2 = whenever possible (tests).  Small K is bound by the appends, not by the matrix pipe, and the
+  // symmetric sweep's hit path is the dearer one (15 kb, symmetric against one-directional: K = 112:
+  // 13.9 / 11.3 ms; K = 192: 17.3 / 15.6; K = 256: 17.4 / 20.0; K = 512: 23.4 / 31.5)
+  int64_t covered = 0;
+  for (const ScreenBlock &sb : p.blocks) covered += sb.nrows;
+  const int cut_r1 = sample_rank(k, SF, P_s, 1, kn);     // (the symmetric sweep has no candidate segments)
+  const int sym_mode = kn.sym(1);
+  if (cut_r1 && all_rows && covered == B && cfg.tt == 1 && cfg.wpb == 4 && cfg.ring >= 2 &&
+      (sym_mode == 2 || (sym_mode == 1 && NK >= 16))) {
+    p.path = ScreenPath::sym;
+    p.SF = SF;
+    p.cut_r = cut_r1;
+    return p;
+  }
+  // the one-directional sweep keeps k + its filter margin inside shortlists of CAP entries: a larger
+  // refsize of a row shard / gonosomal pass goes to the exact kernel
+  if (k > KMAX_ONE_DIR) {
+    p.path = ScreenPath::exact;
+    return p;
+  }
+  p.use_hub1 = hub1;
+  if (hub1) {
+    // (the count pass always runs 128-row blocks in its own configuration; a sweep with two target tiles per
+    //  wave -- WCX_SCREEN_TILE, experiments -- gets its own block list)
+    if (TGT_WG != 128) p.hub_blocks = merge_blocks(exact_blocks, chr_cum, n_chr, 128);
+  } else {
+    p.SF = SF;
+    p.cut_r = sample_rank(k, SF, P_s, n_seg, kn);
+  }
+  return p;
+}
+
+// ---- shared stages
+// The instantiation units of a kernel family each launch the configurations they hold and return -1 for
+// the others: the first unit that holds it launches.
+template <class Unit, size_t N, class... Args>
+static int launch_unit(Unit (&units)[N], const Args &...args) {
+  int rc = -1;
+  for (Unit u : units)
+    if ((rc = u(args...)) >= 0) break;
   return rc;
 }
+static const decltype(&wcx_screen_launch_k1) screen_units[] = {
+    wcx_screen_launch_k1, wcx_screen_launch_k2, wcx_screen_launch_k3, wcx_screen_launch_k4,
+    wcx_screen_launch_k5, wcx_screen_launch_k6, wcx_screen_launch_k7, wcx_screen_launch_k8};
+static const decltype(&wcx_sym_launch_k1) sym_units[] = {wcx_sym_launch_k1, wcx_sym_launch_k2, wcx_sym_launch_k3,
+                                                         wcx_sym_launch_k4, wcx_sym_launch_k5};
+static const decltype(&wcx_count_launch_k1) count_units[] = {wcx_count_launch_k1, wcx_count_launch_k2,
+                                                             wcx_count_launch_k3, wcx_count_launch_k4};
+static const decltype(&wcx_hub1_launch_k1) hub1_units[] = {wcx_hub1_launch_k1, wcx_hub1_launch_k2,
+                                                           wcx_hub1_launch_k3, wcx_hub1_launch_k4};
 
-static int sym_dispatch(int nk, int ctg, int lb, int ring, const SymArgs &a, unsigned grid, size_t lds,
+// A unit launcher's return value as an error code: < 0 = no unit holds the configuration, > 0 = hipError_t
+static int unit_status(int e, const char *family, const ScreenCfg &c, int trials = 0) {
+  if (e == 0) return WCX_OK;
+  char what[128];
+  const int n = snprintf(what, sizeof what, "nk=%d ctg=%d tt=%d wpb=%d lb=%d ring=%d", c.nk, c.ctg, c.tt, c.wpb,
+                         c.lb, c.ring);
+  if (trials) snprintf(what + n, sizeof what - n, " trials=%d", trials);
+  if (e < 0) {
+    wcx_set_error("%s kernel %s is not instantiated", family, what);
+    return (int)WCX_ERR_UNSUPPORTED;
+  }
+  wcx_set_error("%s kernel %s: launch failed: %s", family, what, hipGetErrorString((hipError_t)e));
+  return (int)WCX_ERR_HIP;
+}
+
+// Scratch layout: take(p, bytes) points p at the next offset and moves on by bytes rounded up to 256.
+// A path's layout lambda runs twice: from 0 to size the scratch, then from its base for the pointers.
+struct Carve {
+  uintptr_t at;
+  template <class T> void operator()(T *&p, size_t bytes) {
+    p = reinterpret_cast<T *>(at);
+    at += (bytes + 255) / 256 * 256;
+  }
+};
+
+static float screen_gamma(int NK) { return (float)(16 * NK + 12) * 1.1920929e-7f; }
+
+// Per-sample statistics -- cmean holds mean | min | max | partial sums | partial counts -- and the
+// chromosome table of the kernels
+static int col_stats(const double *dXs, int64_t B, int S, double *cmean, ScreenGlobals *glob,
+                     const int64_t *chr_cum, int n_chr, ChrTab &tab, hipStream_t st) {
+  unsigned long long *cmin = reinterpret_cast<unsigned long long *>(cmean + S);
+  unsigned long long *cmax = cmin + S;
+  double *psum = cmean + 3 * S, *pcnt = psum + (size_t)S * CSPLIT;
+  WCX_HIP(hipMemsetAsync(cmin, 0xff, (size_t)S * 8, st));
+  WCX_HIP(hipMemsetAsync(cmax, 0, (size_t)S * 8, st));
+  k_col_sum<<<dim3((unsigned)S, CSPLIT), NT, 0, st>>>(dXs, B, psum, pcnt, cmin, cmax);
+  k_col_stats<<<(unsigned)((S + 63) / 64), 64, 0, st>>>(S, psum, pcnt, cmin, cmax, cmean, glob);
+  tab.n_chr = n_chr;
+  for (int c = 0; c < 32; ++c) tab.cum[c] = c < n_chr ? chr_cum[c] : B;
+  return WCX_OK;
+}
+
+// Fragments and row info of the sweep positions [0, n_pos) of perm: one workgroup per 32-row tile
+static void screen_prep(int NK, const double *Xr, int64_t n_pos, int S, int Sp, const double *cmean,
+                        const int *perm, ScreenGlobals *glob, half8 *F, RowInfo *info, const unsigned int *gate,
                         hipStream_t st) {
-  int rc = wcx_sym_launch_k1(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_sym_launch_k2(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_sym_launch_k3(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_sym_launch_k4(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_sym_launch_k5(nk, ctg, lb, ring, a, grid, lds, st);
-  return rc;
+  const unsigned g = (unsigned)((n_pos + 31) / 32);
+  switch (NK) {
+#define WCX_PREP_CASE(N) case N: k_screen_prep<N><<<g, NT, 0, st>>>(Xr, n_pos, S, Sp, cmean, perm, glob, F, info, gate); break;
+    WCX_PREP_CASE(1) WCX_PREP_CASE(2) WCX_PREP_CASE(3) WCX_PREP_CASE(4) WCX_PREP_CASE(5)
+    WCX_PREP_CASE(6) WCX_PREP_CASE(7) WCX_PREP_CASE(8) WCX_PREP_CASE(10) WCX_PREP_CASE(12)
+    WCX_PREP_CASE(14) WCX_PREP_CASE(16) WCX_PREP_CASE(20) WCX_PREP_CASE(24) WCX_PREP_CASE(28)
+    WCX_PREP_CASE(40) WCX_PREP_CASE(48) WCX_PREP_CASE(56) WCX_PREP_CASE(64)
+    default: k_screen_prep<32><<<g, NT, 0, st>>>(Xr, n_pos, S, Sp, cmean, perm, glob, F, info, gate); break;
+#undef WCX_PREP_CASE
+  }
+}
+
+// Candidate groups per k_screen launch for a chunk of kb KB of fragments (clamped to 16 .. 4096), and the
+// launch's LDS: the staging ring + the chunk's visit list
+struct ScreenChunk { int64_t groups; size_t lds; };
+static ScreenChunk screen_chunk(const ScreenCfg &cfg, int kb) {
+  int64_t g = ((int64_t)kb << 10) / ((int64_t)cfg.ctg * 32 * cfg.nk * 32);
+  if (g < 16) g = 16;
+  if (g > 4096) g = 4096;
+  return {g, (size_t)(cfg.ring >= 2 ? cfg.ring : 2) * (size_t)(cfg.ctg * cfg.nk * 64) * 16 + (size_t)(g + 64) * 4};
+}
+
+// The final cut of the symmetric sweep over rows [0, n) of rowpos / cnt / flags / Dest
+static int sym_final(int NK, int cap2, const RowInfo *info, const ScreenGlobals *glob, const int *rowpos, int64_t n,
+                     uint2 *sl, int *cnt, unsigned int *flags, const float *Dest, int k, const unsigned int *gate,
+                     hipStream_t st) {
+  const float gamma = screen_gamma(NK);
+  const unsigned gf = (unsigned)((n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536);
+  if (cap2 == CAP2)
+    k_sym_final<CAP2 / 64><<<gf, NT, 0, st>>>(info, glob, rowpos, n, sl, cnt, flags, Dest, k, gamma, CAP, gate);
+  else
+    k_sym_final<CAP2_BIG / 64><<<gf, NT, 0, st>>>(info, glob, rowpos, n, sl, cnt, flags, Dest, k, gamma,
+                                                  REFINE_MAX, gate);
+  WCX_HIP(hipGetLastError());
+  return WCX_OK;
+}
+
+// pending null-sample ranking (auxiliary stream): 0 = start beside the sweep, 1 = beside the
+// refine.  Measured (15 kb, S = 500 / 100): the step takes the same time either way (73.2 / 73.1 ms;
+// serial: 73.6), but beside the sweep the sort's HBM streaming costs the power-limited MFMA loop
+// 6 % (33.4 vs 31.6 ms), beside the refine it costs the refine 2 ms -- so it goes there.
+// (a short refine -- few samples -- cannot hide the 2.4 ms sort: S = 100 is 0.8 ms faster with
+// the sort beside the sweep)
+static bool kick_after_sweep(int S) { return S >= 256; }
+// The sweep order and fragments are queued: ends "topk_prep", starts "topk_screen"
+static int end_prep(wcx_ctx *ctx, int S) {
+  WCX_HIP(hipGetLastError());
+  int rc = wcx_timer_end(ctx, "topk_prep");
+  if (rc) return rc;
+  if (!kick_after_sweep(S) && (rc = wcx_aux_kick(ctx))) return rc;
+  return wcx_timer_begin(ctx, "topk_screen");
+}
+
+// What a sweep leaves for its refine and the exact redo of the rows it could not finish
+struct TopkTail {
+  const double *dXs = nullptr;
+  int64_t B = 0;
+  int S = 0, Sp = 0, k = 0;
+  int cap2 = CAP;                    // list capacity per row (the stride of sl)
+  ChrTab tab;
+  double *Xr = nullptr;
+  ScreenGlobals *glob = nullptr;
+  int *perm = nullptr, *cnt = nullptr;
+  unsigned int *flags = nullptr, *d_nredo = nullptr;
+  unsigned char *searched = nullptr;
+  uint2 *sl = nullptr;
+  TopkBlock *d_redo = nullptr, *d_rtile = nullptr;
+  int32_t *d_rlist = nullptr;
+  void *rscr = nullptr;
+};
+// After the sweep of the rows [r0, r0 + n): the event other streams wait for, the pending ranking (kick),
+// the refine, the device-side redo list and the exact redo; ends the "topk" timer
+static int finish_topk(wcx_ctx *ctx, const TopkTail &t, int64_t r0, int64_t n, bool kick, int32_t *d_out_idx,
+                       double *d_out_dist) {
+  hipStream_t st = ctx->stream;
+  if (ctx->ev_after_sweep) WCX_HIP(hipEventRecord(ctx->ev_after_sweep, st));   // (wcx_sweep_event)
+  int rc = kick ? wcx_aux_kick(ctx) : (int)WCX_OK;
+  if (rc) return rc;
+  rc = wcx_timer_begin(ctx, "topk_refine");
+  if (rc) return rc;
+  rc = wcx_refine_launch(ctx, t.Xr, t.S, t.Sp, t.tab, r0, n, t.searched, t.sl, t.cnt, t.flags, t.perm, t.k,
+                         d_out_idx, d_out_dist, t.glob, t.cap2);
+  if (rc) return rc;
+  rc = wcx_timer_end(ctx, "topk_refine");
+  if (rc) return rc;
+  // rows the screen could not finish (none on all data seen) are redone exactly, device-driven:
+  // redo list and its length never leave the device
+  const unsigned g = (unsigned)((n + NT - 1) / NT);
+  k_collect_redo<<<g, NT, 0, st>>>(r0, n, t.searched, t.flags, t.tab, t.d_redo, t.d_nredo, ctx->d_stats);
+  k_redo_plan<<<1, 64, 0, st>>>(t.tab, t.d_nredo, t.d_rtile);
+  k_redo_fill<<<g, NT, 0, st>>>(r0, n, t.searched, t.flags, t.tab, t.d_nredo, t.d_rlist);
+  WCX_HIP(hipGetLastError());
+  rc = wcx_topk_exact_redo_launch(ctx, t.dXs, t.B, t.S, t.d_redo, t.d_nredo, t.d_rtile, t.d_nredo + 1, t.d_rlist,
+                                  t.rscr, r0, t.k, d_out_idx, d_out_dist);
+  if (rc) return rc;
+  return wcx_timer_end(ctx, "topk");
 }
 
 // Row-sharded symmetric sweep: what phase 1 (wcx_newref_sym_sweep_dev) leaves for the record copy and
 // for phase 2 (wcx_newref_sym_finish_dev); lives in the context (wcx_ctx::sym_state).
 struct SymShardState {
   bool valid = false;
-  int64_t B = 0, row_begin = 0, row_end = 0;
-  int S = 0, Sp = 0, NK = 0, k = 0, cap2 = 0, n_parts = 0, part = 0;
-  ChrTab tab;
+  int64_t row_begin = 0, row_end = 0;
+  int NK = 0, n_parts = 0, part = 0;
   RowBounds rb;
-  const double *dXs = nullptr;
-  double *Xr = nullptr;
+  TopkTail tail;                                 // cnt, flags: of all rows
   RowInfo *info = nullptr;
-  ScreenGlobals *glob = nullptr;
-  int *rowpos = nullptr, *perm = nullptr, *cnt = nullptr;
+  int *rowpos = nullptr;
   float *Dest = nullptr;
-  unsigned int *flags = nullptr, *pool_head = nullptr, *d_nredo = nullptr;
-  unsigned char *searched = nullptr;
-  uint2 *sl = nullptr;
+  unsigned int *pool_head = nullptr;
   uint4 *pool = nullptr;
   unsigned int pool_cap = 0;
   unsigned long long *d_counts = nullptr;       // [32] records per destination | [32] bucket cursors
-  TopkBlock *d_redo = nullptr, *d_rtile = nullptr;
-  int32_t *d_rlist = nullptr;
-  void *rscr = nullptr;
   unsigned long long counts[32] = {0};
   bool overflow = false;                         // this rank's record pool overflowed: the exchange is void
 };
 struct SymShardCall { int part, n_parts; RowBounds rb; SymShardState *state; };
-
-static int count_dispatch(int nk, int ctg, int lb, int ring, const CountArgs &a, unsigned grid, size_t lds,
-                          hipStream_t st) {
-  int rc = wcx_count_launch_k1(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_count_launch_k2(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_count_launch_k3(nk, ctg, lb, ring, a, grid, lds, st);
-  if (rc < 0) rc = wcx_count_launch_k4(nk, ctg, lb, ring, a, grid, lds, st);
-  return rc;
-}
 
 // The search of ALL rows against all rows with the symmetric sweep (screen_sym.h):
 //   order B   all rows by (hub region first, norm class, chromosome), cells padded to tiles: fragments F
@@ -1132,144 +1495,113 @@ static int count_dispatch(int nk, int ctg, int lb, int ring, const CountArgs &a,
 //               streaming top-r -> an estimated threshold per row (its list entries are dropped)
 //     sweep + final cut as above
 //   refine; exact redo of flagged rows
-static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, const int64_t *chr_cum,
-                           int n_chr, const std::vector<ScreenBlock> &blocks, const ScreenCfg &cfg,
-                           int SF, int cut_r, int raw_est, int slots, int k, int32_t *d_out_idx,
-                           double *d_out_dist, SymShardCall *sh = nullptr) {
-  const int NK = cfg.nk, CTG = cfg.ctg, GRr = CTG * 32;
+static int screen_sym_path(wcx_ctx *ctx, const Knobs &kn, const ScreenPlan &p, const double *dXs, int64_t B, int S,
+                           const int64_t *chr_cum, int n_chr, int k, int32_t *d_out_idx, double *d_out_dist,
+                           SymShardCall *sh = nullptr) {
+  const ScreenCfg &cfg = p.cfg;
+  const std::vector<ScreenBlock> &blocks = p.blocks;
+  const int NK = cfg.nk, CTG = cfg.ctg, SF = p.SF;
   const int Sp = row_pitch(S);
   const int64_t n_rows = B;
   const int64_t n_own = sh ? sh->rb.b[sh->part + 1] - sh->rb.b[sh->part] : B;   // rows whose lists live here
   // list capacity per row: the estimates admit ~4 k entries at k = 300, ~2.7 k at k = 1000
   const int cap2 = k <= 448 ? CAP2 : CAP2_BIG;
-  // hub-count estimates (attempt 1): WCX_SYM_HUB=0 turns them off; the region is 1 / WCX_HUB_FRAC of the
-  // rows, at least 8 x the entries wanted (+ 512) below an estimate (1.18 k: the k-th neighbour's filter bound
-  // ranks ~1.14 k)
-  // (WCX_HUB_TEST_FAIL=1, tests: a count nobody reaches -- every row ends without an estimate, the verdict
-  //  opens the gate and the second attempt must deliver the same bits)
-  const int need = env_int("WCX_HUB_TEST_FAIL", 0) ? (1 << 28) : (int)(1.18 * k) + 8;
-  // (few samples: the distances are noisier and the neighbours less concentrated on the low-norm rows --
-  //  two thirds of them in the lowest 1/16 at S = 100 against 98 % at S = 500: a larger region)
-  const int hub_frac = env_int("WCX_HUB_FRAC", NK >= 16 ? 32 : 12);
-  int64_t hub_rows = hub_frac > 1 ? B / hub_frac : 0;
-  // (at least 8 x the entries wanted + the 512 candidates of the moment phase: the loosest trial sits at
-  //  4 x need among what is left after the row's own chromosome is taken out)
-  const int64_t need_real = (int64_t)(1.18 * k) + 8;
-  if (hub_rows < 8 * need_real + 512) hub_rows = 8 * need_real + 512;
-  const bool use_hub = env_int("WCX_SYM_HUB", 1) != 0 && NK >= 5 && hub_frac > 1 && hub_rows * 6 <= B;
+  // hub-count estimates (attempt 1), WCX_SYM_HUB=0 turns them off
+  // (WCX_HUB_TEST_FAIL=1, tests: every row ends without an estimate, the verdict opens the gate and the
+  //  second attempt must deliver the same bits)
+  const bool use_hub = kn.sym_hub(1) != 0 && p.hub_ok;
   if (sh && !use_hub) {
     wcx_set_error("the row-sharded symmetric sweep needs the hub-count thresholds (K >= 256, B >= %lld)",
-                  (long long)(36 * (int64_t)need));
+                  (long long)(36 * (int64_t)p.hub_need));
     return (int)WCX_ERR_UNSUPPORTED;
   }
-  const int n1_tiles = env_int("WCX_HUB_N1", 16);
   const int64_t n_s = (B + SF - 1) / SF;
   const int64_t P_s = (n_s + CT - 1) / CT * CT;
   const int64_t Bpad2 = P_s + ((B - n_s) + CT - 1) / CT * CT;       // positions of the two-region order
   const int64_t NTb = (((B + 31) / 32 + (int64_t)2 * SYM_NCLS * n_chr + 4) + 7) / 8 * 8;   // tile bound
   const int64_t PB = NTb * 32;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_glob = carve(sizeof(ScreenGlobals));
-  const size_t o_mean = carve((size_t)S * 8 * (3 + 2 * CSPLIT));   // mean | min | max | partial sums | partial counts
-  const size_t o_xr = carve((size_t)B * Sp * 8 + 256);
-  const size_t o_F = carve((size_t)PB * NK * 32);
-  const size_t o_Fs = carve((size_t)P_s * NK * 32);
-  const size_t o_info = carve((size_t)PB * sizeof(RowInfo));
-  const size_t o_infs = carve((size_t)P_s * sizeof(RowInfo));
-  const size_t o_perm = carve((size_t)PB * 4);
-  const size_t o_perm2 = carve((size_t)Bpad2 * 4);
-  const size_t o_rpos = carve((size_t)B * 4);
-  const size_t o_rpos2 = carve((size_t)B * 4);
-  const size_t o_rbit = carve((size_t)B * 4);
-  const size_t o_rfin = carve((size_t)B * 4);
-  const size_t o_hubh = carve((size_t)HUB_BINS * 4);
-  const size_t o_rchr = carve((size_t)B * 4);
-  const size_t o_rkey = carve((size_t)B * 4);
-  const size_t o_cell = carve((size_t)2 * NCELL * 4);
-  const size_t o_curs = carve((size_t)2 * NCELL * 4);
-  const size_t o_gmsk = carve((size_t)(P_s / CT) * 4);
-  const size_t o_tinf = carve((size_t)NTb * 64 * 4);
-  const size_t o_tmin = carve((size_t)NTb * 4);
-  const size_t o_tchr = carve((size_t)NTb);
-  const size_t o_dest = carve((size_t)n_rows * 4);
   // records: row-direction hits (a few per cent of all) + everything from launches that split a
   // target quad over several work items (the high, hub-free tiles)
   // (a small matrix splits most of its chunks: nearly every hit is a record then -- half a list per row)
   const int64_t pool_want = sh ? n_rows * (int64_t)(cap2 / 2) / sh->n_parts * 2 : n_rows * (int64_t)(cap2 / 2);
   const unsigned int pool_cap = (unsigned int)(pool_want < 200000000ll ? pool_want : 200000000ll);
-  const size_t o_pool = carve((size_t)pool_cap * 16);
-  const size_t o_phead = carve(256);      // pool head | pool overflow | queue head | gate | failed rows
-  const size_t o_desc = carve(256 * sizeof(SymDesc));
-  const size_t o_seq = carve((size_t)(NTb / 4 + 1) * 4);
-  const size_t o_sl = carve((size_t)n_own * cap2 * 8);
   const int n_wg_det = (int)((B + NT - 1) / NT);
-  const size_t o_dett = carve(sh ? (size_t)DET_KEYS * n_wg_det * 4 : 0);
-  const size_t o_detl = carve(sh ? (size_t)B * 2 : 0);
-  const size_t o_cnts = carve(64 * 8);
-  const size_t o_cnt = carve((size_t)n_rows * 4);
-  const size_t o_gst = carve((size_t)n_rows * 4);
-  const size_t o_flag = carve((size_t)n_rows * 4);
-  const size_t o_srch = carve((size_t)n_rows);
-  const size_t o_blk = carve(blocks.size() * sizeof(ScreenBlock));
-  const size_t o_redo = carve((size_t)n_rows * sizeof(TopkBlock));
-  const size_t o_nredo = carve(512);
-  const size_t o_rtile = carve(((size_t)n_rows / 64 + 64) * sizeof(TopkBlock));
-  const size_t o_rlist = carve((size_t)n_rows * 4);
-  const size_t o_rscr = carve(wcx_topk_redo_scratch_bytes(k, B));
+  TopkTail t;
+  ScreenGlobals *glob;
+  double *cmean;
+  half8 *F, *Fs;
+  RowInfo *info, *infs;
+  int *perm2, *rowpos, *rowpos2, *hubhist, *rchr, *rkey, *cellcnt, *cursor, *d_seq, *dett;
+  unsigned int *rbits, *rfine, *gmask, *tinfo, *pool_head;
+  float *tmin, *Dest, *g_state;
+  unsigned char *tchr;
+  unsigned short *detl;
+  uint4 *pool;
+  SymDesc *d_desc;
+  unsigned long long *d_counts;
+  ScreenBlock *d_blocks;
+  auto layout = [&](uintptr_t base) {
+    Carve take{base};
+    take(glob, sizeof(ScreenGlobals));
+    take(cmean, (size_t)S * 8 * (3 + 2 * CSPLIT));
+    take(t.Xr, (size_t)B * Sp * 8 + 256);
+    take(F, (size_t)PB * NK * 32);
+    take(Fs, (size_t)P_s * NK * 32);
+    take(info, (size_t)PB * sizeof(RowInfo));
+    take(infs, (size_t)P_s * sizeof(RowInfo));
+    take(t.perm, (size_t)PB * 4);
+    take(perm2, (size_t)Bpad2 * 4);
+    take(rowpos, (size_t)B * 4);
+    take(rowpos2, (size_t)B * 4);
+    take(rbits, (size_t)B * 4);
+    take(rfine, (size_t)B * 4);
+    take(hubhist, (size_t)HUB_BINS * 4);
+    take(rchr, (size_t)B * 4);
+    take(rkey, (size_t)B * 4);
+    take(cellcnt, (size_t)2 * NCELL * 4);
+    take(cursor, (size_t)2 * NCELL * 4);
+    take(gmask, (size_t)(P_s / CT) * 4);
+    take(tinfo, (size_t)NTb * 64 * 4);
+    take(tmin, (size_t)NTb * 4);
+    take(tchr, (size_t)NTb);
+    take(Dest, (size_t)n_rows * 4);
+    take(pool, (size_t)pool_cap * 16);
+    take(pool_head, 256);      // pool head | pool overflow | queue head | gate | failed rows
+    take(d_desc, 256 * sizeof(SymDesc));
+    take(d_seq, (size_t)(NTb / 4 + 1) * 4);
+    take(t.sl, (size_t)n_own * cap2 * 8);
+    take(dett, sh ? (size_t)DET_KEYS * n_wg_det * 4 : 0);
+    take(detl, sh ? (size_t)B * 2 : 0);
+    take(d_counts, 64 * 8);
+    take(t.cnt, (size_t)n_rows * 4);
+    take(g_state, (size_t)n_rows * 4);
+    take(t.flags, (size_t)n_rows * 4);
+    take(t.searched, (size_t)n_rows);
+    take(d_blocks, blocks.size() * sizeof(ScreenBlock));
+    take(t.d_redo, (size_t)n_rows * sizeof(TopkBlock));
+    take(t.d_nredo, 512);
+    take(t.d_rtile, ((size_t)n_rows / 64 + 64) * sizeof(TopkBlock));
+    take(t.d_rlist, (size_t)n_rows * 4);
+    take(t.rscr, wcx_topk_redo_scratch_bytes(k, B));
+    return (size_t)(take.at - base);
+  };
   void *scr = nullptr;
-  int rc = wcx_scratch(ctx, off, &scr);
+  int rc = wcx_scratch(ctx, layout(0), &scr);
   if (rc) return rc;
-  char *base = reinterpret_cast<char *>(scr);
-  ScreenGlobals *glob = reinterpret_cast<ScreenGlobals *>(base + o_glob);
-  double *cmean = reinterpret_cast<double *>(base + o_mean);
-  double *Xr = reinterpret_cast<double *>(base + o_xr);
-  half8 *F = reinterpret_cast<half8 *>(base + o_F);
-  half8 *Fs = reinterpret_cast<half8 *>(base + o_Fs);
-  RowInfo *info = reinterpret_cast<RowInfo *>(base + o_info);
-  RowInfo *infs = reinterpret_cast<RowInfo *>(base + o_infs);
-  int *perm = reinterpret_cast<int *>(base + o_perm);
-  int *perm2 = reinterpret_cast<int *>(base + o_perm2);
-  int *rowpos = reinterpret_cast<int *>(base + o_rpos);
-  int *rowpos2 = reinterpret_cast<int *>(base + o_rpos2);
-  unsigned int *rbits = reinterpret_cast<unsigned int *>(base + o_rbit);
-  unsigned int *rfine = reinterpret_cast<unsigned int *>(base + o_rfin);
-  int *hubhist = reinterpret_cast<int *>(base + o_hubh);
-  int *rchr = reinterpret_cast<int *>(base + o_rchr);
-  int *rkey = reinterpret_cast<int *>(base + o_rkey);
-  int *cellcnt = reinterpret_cast<int *>(base + o_cell);
-  int *cursor = reinterpret_cast<int *>(base + o_curs);
-  unsigned int *gmask = reinterpret_cast<unsigned int *>(base + o_gmsk);
-  unsigned int *tinfo = reinterpret_cast<unsigned int *>(base + o_tinf);
-  float *tmin = reinterpret_cast<float *>(base + o_tmin);
-  unsigned char *tchr = reinterpret_cast<unsigned char *>(base + o_tchr);
-  float *Dest = reinterpret_cast<float *>(base + o_dest);
-  uint4 *pool = reinterpret_cast<uint4 *>(base + o_pool);
-  unsigned int *pool_head = reinterpret_cast<unsigned int *>(base + o_phead);
+  layout(reinterpret_cast<uintptr_t>(scr));
+  t.dXs = dXs; t.B = B; t.S = S; t.Sp = Sp; t.k = k; t.cap2 = cap2; t.glob = glob;
   unsigned int *d_gate = pool_head + 3, *d_failed = pool_head + 4;
-  SymDesc *d_desc = reinterpret_cast<SymDesc *>(base + o_desc);
-  int *d_seq = reinterpret_cast<int *>(base + o_seq);
-  uint2 *sl = reinterpret_cast<uint2 *>(base + o_sl);
-  int *cnt_out = reinterpret_cast<int *>(base + o_cnt);
-  float *g_state = reinterpret_cast<float *>(base + o_gst);
-  unsigned int *flags = reinterpret_cast<unsigned int *>(base + o_flag);
-  unsigned char *searched = reinterpret_cast<unsigned char *>(base + o_srch);
-  ScreenBlock *d_blocks = reinterpret_cast<ScreenBlock *>(base + o_blk);
-  TopkBlock *d_redo = reinterpret_cast<TopkBlock *>(base + o_redo);
-  unsigned int *d_nredo = reinterpret_cast<unsigned int *>(base + o_nredo);
-  TopkBlock *d_rtile = reinterpret_cast<TopkBlock *>(base + o_rtile);
-  int32_t *d_rlist = reinterpret_cast<int32_t *>(base + o_rlist);
   // the gate of the second attempt: closed until the verdict opens it; without a first attempt the
   // second one is the only one and runs ungated
   const unsigned int *gate2 = use_hub ? d_gate : nullptr;
 
   hipStream_t st = ctx->stream;
   WCX_HIP(hipMemsetAsync(glob, 0, sizeof(ScreenGlobals), st));
-  WCX_HIP(hipMemsetAsync(cnt_out, 0, (size_t)n_rows * 4, st));
-  WCX_HIP(hipMemsetAsync(flags, 0, (size_t)n_rows * 4, st));
-  WCX_HIP(hipMemsetAsync(searched, 1, (size_t)n_rows, st));          // every row is a target
+  WCX_HIP(hipMemsetAsync(t.cnt, 0, (size_t)n_rows * 4, st));
+  WCX_HIP(hipMemsetAsync(t.flags, 0, (size_t)n_rows * 4, st));
+  WCX_HIP(hipMemsetAsync(t.searched, 1, (size_t)n_rows, st));          // every row is a target
   WCX_HIP(hipMemsetAsync(pool_head, 0, 256, st));
-  WCX_HIP(hipMemsetAsync(d_nredo, 0, 512, st));
+  WCX_HIP(hipMemsetAsync(t.d_nredo, 0, 512, st));
   WCX_HIP(hipMemsetAsync(ctx->d_stats, 0, 256, st));
   rc = wcx_upload_small(ctx, d_blocks, blocks.data(), blocks.size() * sizeof(ScreenBlock));
   if (rc) return rc;
@@ -1278,69 +1610,37 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
   if (rc) return rc;
   rc = wcx_timer_begin(ctx, "topk_prep");
   if (rc) return rc;
-  unsigned long long *cmin = reinterpret_cast<unsigned long long *>(cmean + S);
-  unsigned long long *cmax = cmin + S;
-  double *psum = cmean + 3 * S, *pcnt = psum + (size_t)S * CSPLIT;
-  WCX_HIP(hipMemsetAsync(cmin, 0xff, (size_t)S * 8, st));
-  WCX_HIP(hipMemsetAsync(cmax, 0, (size_t)S * 8, st));
-  k_col_sum<<<dim3((unsigned)S, CSPLIT), NT, 0, st>>>(dXs, B, psum, pcnt, cmin, cmax);
-  k_col_stats<<<(unsigned)((S + 63) / 64), 64, 0, st>>>(S, psum, pcnt, cmin, cmax, cmean, glob);
-  ChrTab tab;
-  tab.n_chr = n_chr;
-  for (int c = 0; c < 32; ++c) tab.cum[c] = c < n_chr ? chr_cum[c] : B;
+  rc = col_stats(dXs, B, S, cmean, glob, chr_cum, n_chr, t.tab, st);
+  if (rc) return rc;
+  const ChrTab &tab = t.tab;
   const unsigned gb = (unsigned)((B + NT - 1) / NT);
   if (use_hub) {
     WCX_HIP(hipMemsetAsync(hubhist, 0, (size_t)HUB_BINS * 4, st));
-    k_transpose_norm<<<(unsigned)((B + 31) / 32), 256, 0, st>>>(dXs, B, S, Sp, Xr, cmean, tab, glob, rbits, rchr,
+    k_transpose_norm<<<(unsigned)((B + 31) / 32), 256, 0, st>>>(dXs, B, S, Sp, t.Xr, cmean, tab, glob, rbits, rchr,
                                                                 rfine, hubhist);
-    k_hub_cut<<<1, 1024, 0, st>>>(hubhist, (int)hub_rows, glob);
+    k_hub_cut<<<1, 1024, 0, st>>>(hubhist, (int)p.hub_rows, glob);
   } else {
-    k_transpose_norm<<<(unsigned)((B + 31) / 32), 256, 0, st>>>(dXs, B, S, Sp, Xr, cmean, tab, glob, rbits, rchr,
+    k_transpose_norm<<<(unsigned)((B + 31) / 32), 256, 0, st>>>(dXs, B, S, Sp, t.Xr, cmean, tab, glob, rbits, rchr,
                                                                 nullptr, nullptr);
   }
   // order B: (hub region | the rest) x (norm class, chromosome) cells padded to tiles
   WCX_HIP(hipMemsetAsync(cellcnt, 0, (size_t)2 * NCELL * 4, st));
   WCX_HIP(hipMemsetAsync(cursor, 0, (size_t)2 * NCELL * 4, st));
-  WCX_HIP(hipMemsetAsync(perm, 0xff, (size_t)PB * 4, st));
+  WCX_HIP(hipMemsetAsync(t.perm, 0xff, (size_t)PB * 4, st));
   WCX_HIP(hipMemsetAsync(tchr, 0xff, (size_t)NTb, st));
   static_assert(2 * SYM_NCELL * SYM_NSUB <= 2 * NCELL, "cell tables");
-  k_sym_hist<<<gb, NT, 0, st>>>(rbits, rchr, B, glob, rkey, cellcnt, env_int("WCX_SYM_SUBORDER", 1),
-                                use_hub ? rfine : nullptr);
+  k_sym_hist<<<gb, NT, 0, st>>>(rbits, rchr, B, glob, rkey, cellcnt, 1, use_hub ? rfine : nullptr);
   k_sym_scan<<<1, SYM_NCELL, 0, st>>>(cellcnt, cursor, tchr, glob);
   if (sh) {      // the same order on every rank
-    int *dett = reinterpret_cast<int *>(base + o_dett);
-    unsigned short *detl = reinterpret_cast<unsigned short *>(base + o_detl);
     WCX_HIP(hipMemsetAsync(dett, 0, (size_t)DET_KEYS * n_wg_det * 4, st));
     k_det_local<<<gb, NT, 0, st>>>(rkey, B, n_wg_det, dett, detl);
     k_det_scan<<<(unsigned)((DET_KEYS * 64 + NT - 1) / NT), NT, 0, st>>>(dett, n_wg_det, cursor);
-    k_det_place<<<gb, NT, 0, st>>>(rkey, B, n_wg_det, dett, detl, perm, rowpos);
+    k_det_place<<<gb, NT, 0, st>>>(rkey, B, n_wg_det, dett, detl, t.perm, rowpos);
   } else {
-    k_scatter<<<gb, NT, 0, st>>>(rkey, B, cursor, perm, rowpos);
+    k_scatter<<<gb, NT, 0, st>>>(rkey, B, cursor, t.perm, rowpos);
   }
-  const unsigned gprep = (unsigned)((PB + NT - 1) / NT), gprep_s = (unsigned)((P_s + NT - 1) / NT);
-  auto prep_frag = [&](int64_t n_pos, const int *pm, half8 *Fo, RowInfo *io, const unsigned int *gate) {
-    const unsigned g = (unsigned)((n_pos + 31) / 32);            // one workgroup per 32-row tile
-    switch (NK) {
-#define WCX_PREP_CASE(N) case N: k_screen_prep<N><<<g, NT, 0, st>>>(Xr, n_pos, S, Sp, cmean, pm, glob, Fo, io, gate); break;
-      WCX_PREP_CASE(1) WCX_PREP_CASE(2) WCX_PREP_CASE(3) WCX_PREP_CASE(4) WCX_PREP_CASE(5)
-      WCX_PREP_CASE(6) WCX_PREP_CASE(7) WCX_PREP_CASE(8) WCX_PREP_CASE(10) WCX_PREP_CASE(12)
-      WCX_PREP_CASE(14) WCX_PREP_CASE(16) WCX_PREP_CASE(20) WCX_PREP_CASE(24) WCX_PREP_CASE(28)
-      WCX_PREP_CASE(40) WCX_PREP_CASE(48) WCX_PREP_CASE(56) WCX_PREP_CASE(64)
-      default: k_screen_prep<32><<<g, NT, 0, st>>>(Xr, n_pos, S, Sp, cmean, pm, glob, Fo, io, gate); break;
-#undef WCX_PREP_CASE
-    }
-  };
-  (void)gprep_s;
-  prep_frag(PB, perm, F, info, nullptr);
-  WCX_HIP(hipGetLastError());
-  rc = wcx_timer_end(ctx, "topk_prep");
-  if (rc) return rc;
-  const int kick_at = env_int("WCX_RANK_KICK", S >= 256 ? 1 : 0);
-  if (kick_at == 0) {
-    rc = wcx_aux_kick(ctx);
-    if (rc) return rc;
-  }
-  rc = wcx_timer_begin(ctx, "topk_screen");
+  screen_prep(NK, t.Xr, PB, S, Sp, cmean, t.perm, glob, F, info, nullptr, st);
+  rc = end_prep(ctx, S);
   if (rc) return rc;
 
   // ---- the symmetric sweep: ONE persistent launch; the workgroups pull (chunk, quad) work items from a
@@ -1351,7 +1651,7 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
   // (a chunk that fits an XCD's 4 MB L2 is fetched once per XCD and round of workgroups; an 8 MB chunk --
   //  the round-4 default at K = 512 -- cycles through it: 45.4 GB fetched per sweep against 16.6 GB at
   //  3 MB, 21.5 against 20.9 ms; 1.5 / 2 / 4 MB: 19.3 / 16.8 / 21.8 GB: scripts/sweep_sym_chunk_traffic.sh)
-  int64_t Cz = ((int64_t)env_int("WCX_SYM_CHUNK_KB", 3072) << 10) / ((int64_t)NK * 1024);
+  int64_t Cz = ((int64_t)kn.sym_chunk_kb(3072) << 10) / ((int64_t)NK * 1024);
   Cz = Cz / 8 * 8;
   if (Cz < 32) Cz = 32;
   if (Cz > 8192) Cz = 8192;
@@ -1363,8 +1663,7 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
   SymArgs sa;
   int sym_grid = 0;
   {
-    const int split_env = env_int("WCX_SYM_SPLIT", 0);
-    const int fill = env_int("WCX_SYM_FILL", 1) * slots;        // work items a chunk should offer
+    const int fill = kn.sym_fill(1) * p.slots;        // work items a chunk should offer
     std::vector<SymDesc> descs;
     int total = 0;
     for (int64_t c0 = 0; c0 < NTb; c0 += Cz) {
@@ -1376,7 +1675,8 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
       int n_split = d.n_q >= fill ? 1 : (fill + d.n_q - 1) / d.n_q;
       const int max_split = (d.c1 - d.c0) / CTG / 8 > 1 ? (d.c1 - d.c0) / CTG / 8 : 1;
       if (n_split > max_split) n_split = max_split;
-      if (split_env > 0) n_split = split_env < max_split ? split_env : max_split;
+      const int split = kn.sym_split(0);
+      if (split > 0) n_split = split < max_split ? split : max_split;
       if (n_split < 1) n_split = 1;
       if (!descs.empty() && n_split < descs.back().n_split) n_split = descs.back().n_split;   // (monotone:
       d.n_split = n_split;                          //  a quad's exclusive items are its chunks 0 .. L - 1)
@@ -1389,40 +1689,27 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
     rc = wcx_upload_small(ctx, d_desc, descs.data(), descs.size() * sizeof(SymDesc));
     if (rc) return rc;
     WCX_HIP(hipMemsetAsync(d_seq, 0, (size_t)(NQb + 1) * 4, st));
-    sa.F = F; sa.tinfo = tinfo; sa.tmin = tmin; sa.tchr = tchr; sa.glob = glob; sa.sl = sl; sa.cnt = cnt_out;
-    sa.flags = flags; sa.stats = ctx->d_stats; sa.dbg = ctx->debug_flags; sa.cap2 = cap2;
+    sa.F = F; sa.tinfo = tinfo; sa.tmin = tmin; sa.tchr = tchr; sa.glob = glob; sa.sl = t.sl; sa.cnt = t.cnt;
+    sa.flags = t.flags; sa.stats = ctx->d_stats; sa.dbg = ctx->debug_flags; sa.cap2 = cap2;
     sa.pool = pool; sa.pool_head = pool_head; sa.pool_ovf = pool_head + 1; sa.pool_cap = pool_cap;
     sa.queue_head = pool_head + 2;
     sa.desc = d_desc; sa.n_desc = (int)descs.size(); sa.total_items = total; sa.seq = d_seq;
     sa.glist_cap = glist_cap;
     sa.gate = nullptr;
     if (sh) { sa.force_records = 1; sa.part = sh->part; sa.n_parts = sh->n_parts; }
-    sym_grid = total < slots ? total : slots;
+    sym_grid = total < p.slots ? total : p.slots;
   }
-  const float gamma = (float)(16 * NK + 12) * 1.1920929e-7f;
-  const unsigned gf = (unsigned)((n_rows + 3) / 4 < 65536 ? (n_rows + 3) / 4 : 65536);
+  auto sweep = [&]() {
+    return unit_status(launch_unit(sym_units, NK, CTG, cfg.lb, cfg.ring, sa, (unsigned)sym_grid, lds_sym, st),
+                       "symmetric screen", cfg);
+  };
   auto sweep_and_cut = [&](const unsigned int *gate) -> int {
     sa.gate = gate;
-    const int e = sym_dispatch(NK, CTG, cfg.lb, cfg.ring, sa, (unsigned)sym_grid, lds_sym, st);
-    if (e < 0) {
-      wcx_set_error("symmetric screen kernel nk=%d ctg=%d lb=%d ring=%d is not instantiated", NK, CTG, cfg.lb,
-                    cfg.ring);
-      return (int)WCX_ERR_UNSUPPORTED;
-    }
-    if (e != 0) {
-      wcx_set_error("symmetric screen kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      return (int)WCX_ERR_HIP;
-    }
-    k_sym_regroup<<<2048, NT, 0, st>>>(pool, pool_head, pool_head + 1, pool_cap, n_rows, sl, cnt_out, flags,
+    const int e = sweep();
+    if (e) return e;
+    k_sym_regroup<<<2048, NT, 0, st>>>(pool, pool_head, pool_head + 1, pool_cap, n_rows, t.sl, t.cnt, t.flags,
                                        cap2, gate);
-    if (cap2 == CAP2)
-      k_sym_final<CAP2 / 64><<<gf, NT, 0, st>>>(info, glob, rowpos, n_rows, sl, cnt_out, flags, Dest, k, gamma,
-                                                CAP, gate);
-    else
-      k_sym_final<CAP2_BIG / 64><<<gf, NT, 0, st>>>(info, glob, rowpos, n_rows, sl, cnt_out, flags, Dest, k,
-                                                    gamma, REFINE_MAX, gate);
-    WCX_HIP(hipGetLastError());
-    return (int)WCX_OK;
+    return sym_final(NK, cap2, info, glob, rowpos, n_rows, t.sl, t.cnt, t.flags, Dest, k, gate, st);
   };
 
   // ---- attempt 1: thresholds from the hub counts
@@ -1430,41 +1717,25 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
     rc = wcx_timer_begin(ctx, "topk_pre");
     if (rc) return rc;
     CountArgs ca;
-    ca.F = F; ca.tchr = tchr; ca.glob = glob; ca.perm = perm; ca.tinfo = tinfo; ca.tmin = tmin;
-    ca.Dest = Dest; ca.cnt = cnt_out; ca.flags = flags; ca.stats = ctx->d_stats;
-    ca.need = need; ca.n1 = n1_tiles; ca.gate = nullptr;
-    const bool hub_pass = env_int("WCX_HUB_APPEND", 0) != 0 && !(ctx->debug_flags & 123) && !sh;
-    ca.sl = hub_pass ? sl : nullptr; ca.cap2 = cap2;
-    sa.hub_appended = hub_pass ? 1 : 0;
+    ca.F = F; ca.tchr = tchr; ca.glob = glob; ca.perm = t.perm; ca.tinfo = tinfo; ca.tmin = tmin;
+    ca.Dest = Dest; ca.cnt = t.cnt; ca.flags = t.flags; ca.stats = ctx->d_stats;
+    ca.need = p.hub_need; ca.n1 = kn.hub_n1(16); ca.gate = nullptr;
+    ca.sl = nullptr; ca.cap2 = cap2;
     // the visit list holds the hub groups only: room for twice the rows asked for (the quantile takes a
     // whole histogram bin) + one padding tile per cell; a bigger region is cut off there by the kernel
-    const int64_t hub_t = (hub_rows * 2 + 31) / 32 + (int64_t)SYM_NCLS * n_chr + 8;
+    const int64_t hub_t = (p.hub_rows * 2 + 31) / 32 + (int64_t)SYM_NCLS * n_chr + 8;
     const int64_t cap_t = hub_t < NTb ? hub_t : NTb;
     ca.glist_cap = (int)(cap_t / CTG + 64);
     const size_t lds_cnt = (size_t)cfg.ring * (size_t)(CTG * NK * 64) * 16 + (size_t)ca.glist_cap * 4;
-    int e = count_dispatch(NK, CTG, cfg.lb, cfg.ring, ca, (unsigned)NQb, lds_cnt, st);
-    if (e == 0 && hub_pass) {
-      ca.append_pass = 1;
-      e = count_dispatch(NK, CTG, cfg.lb, cfg.ring, ca, (unsigned)NQb, lds_cnt, st);
-    }
-    if (e < 0) {
-      wcx_set_error("hub-count kernel nk=%d ctg=%d lb=%d ring=%d is not instantiated", NK, CTG, cfg.lb, cfg.ring);
-      return (int)WCX_ERR_UNSUPPORTED;
-    }
-    if (e != 0) {
-      wcx_set_error("hub-count kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      return (int)WCX_ERR_HIP;
-    }
+    rc = unit_status(launch_unit(count_units, NK, CTG, cfg.lb, cfg.ring, ca, (unsigned)NQb, lds_cnt, st),
+                     "hub-count", cfg);
+    if (rc) return rc;
     rc = wcx_timer_end(ctx, "topk_pre");
     if (rc) return rc;
     if (sh) {
       // this rank's tile pairs -> records; how many go to which rank (the call synchronises here)
-      const int e2 = sym_dispatch(NK, CTG, cfg.lb, cfg.ring, sa, (unsigned)sym_grid, lds_sym, st);
-      if (e2 != 0) {
-        wcx_set_error("symmetric screen kernel nk=%d ctg=%d: launch failed (%d)", NK, CTG, e2);
-        return e2 < 0 ? (int)WCX_ERR_UNSUPPORTED : (int)WCX_ERR_HIP;
-      }
-      unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + o_cnts);
+      rc = sweep();
+      if (rc) return rc;
       WCX_HIP(hipMemsetAsync(d_counts, 0, 64 * 8, st));
       k_rec_hist<<<1024, NT, 0, st>>>(pool, pool_head, pool_cap, sh->rb, d_counts);
       WCX_HIP(hipGetLastError());
@@ -1481,26 +1752,24 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
       // rows with the exact kernel (wcx_newref_sym_finish_dev, n_recv < 0): the unsharded path's answer to
       // the same overflow.  No rank raises alone, nobody is left waiting in a collective.
       // (WCX_SYM_TEST_POOL_OVF=1, tests: as if the pool had overflowed)
-      Z.overflow = head2[1] || head2[0] > pool_cap || env_int("WCX_SYM_TEST_POOL_OVF", 0) != 0;
+      Z.overflow = head2[1] || head2[0] > pool_cap || kn.pool_ovf(0) != 0;
       if (Z.overflow)
         for (int r = 0; r < 32; ++r) Z.counts[r] = 0;
       Z.valid = true;
-      Z.B = B; Z.row_begin = sh->rb.b[sh->part]; Z.row_end = sh->rb.b[sh->part + 1];
-      Z.S = S; Z.Sp = Sp; Z.NK = NK; Z.k = k; Z.cap2 = cap2; Z.n_parts = sh->n_parts; Z.part = sh->part;
-      Z.tab = tab; Z.rb = sh->rb; Z.dXs = dXs; Z.Xr = Xr; Z.info = info; Z.glob = glob; Z.rowpos = rowpos;
-      Z.perm = perm; Z.cnt = cnt_out; Z.Dest = Dest; Z.flags = flags; Z.pool_head = pool_head;
-      Z.d_nredo = d_nredo; Z.searched = searched; Z.sl = sl; Z.pool = pool; Z.pool_cap = pool_cap;
-      Z.d_counts = d_counts; Z.d_redo = d_redo; Z.d_rtile = d_rtile; Z.d_rlist = d_rlist;
-      Z.rscr = base + o_rscr;
+      Z.row_begin = sh->rb.b[sh->part]; Z.row_end = sh->rb.b[sh->part + 1];
+      Z.NK = NK; Z.n_parts = sh->n_parts; Z.part = sh->part; Z.rb = sh->rb;
+      Z.tail = t; Z.info = info; Z.rowpos = rowpos; Z.Dest = Dest;
+      Z.pool_head = pool_head; Z.pool = pool; Z.pool_cap = pool_cap; Z.d_counts = d_counts;
       return (int)WCX_OK;
     }
     rc = sweep_and_cut(nullptr);
     if (rc) return rc;
-    if (!(ctx->debug_flags & 123)) {      // (the ablations leave every row unfinished: one sweep is what they time)
-      k_hub_count_failed<<<512, NT, 0, st>>>(flags, n_rows, d_failed);
+    // (the ablations leave every row unfinished: one sweep is what they time)
+    if (!(ctx->debug_flags & DBG_ABLATIONS)) {
+      k_hub_count_failed<<<512, NT, 0, st>>>(t.flags, n_rows, d_failed);
       k_hub_verdict<<<1, 64, 0, st>>>(d_failed, d_gate, ctx->d_stats);
     }
-    k_gate_reset<<<1024, NT, 0, st>>>(d_gate, n_rows, cnt_out, flags, pool_head, d_seq, NQb + 1);
+    k_gate_reset<<<1024, NT, 0, st>>>(d_gate, n_rows, t.cnt, t.flags, pool_head, d_seq, NQb + 1);
   } else {
     rc = wcx_timer_begin(ctx, "topk_pre");
     if (rc) return rc;
@@ -1515,404 +1784,151 @@ static int screen_sym_path(wcx_ctx *ctx, const double *dXs, int64_t B, int S, co
     k_scan_cells<<<1, 1024, 0, st>>>(cellcnt, cursor, (int)(P_s - n_s), gate2);
     k_scatter<<<gb, NT, 0, st>>>(rkey, B, cursor, perm2, rowpos2, gate2);
     k_group_mask<<<(unsigned)((P_s / CT + NT - 1) / NT), NT, 0, st>>>(perm2, rchr, P_s / CT, gmask, gate2);
-    prep_frag(P_s, perm2, Fs, infs, gate2);
+    screen_prep(NK, t.Xr, P_s, S, Sp, cmean, perm2, glob, Fs, infs, gate2, st);
     WCX_HIP(hipGetLastError());
-    const int64_t group_bytes = (int64_t)GRr * NK * 32;
-    int64_t chunk_groups = ((int64_t)env_int("WCX_SCREEN_CHUNK_KB", NK > 16 ? 16384 : 3072) << 10) / group_bytes;
-    if (chunk_groups < 16) chunk_groups = 16;
-    if (chunk_groups > 4096) chunk_groups = 4096;
-    const size_t lds = (size_t)(cfg.ring >= 2 ? cfg.ring : 2) * (size_t)(CTG * NK * 64) * 16 +
-                       (size_t)(chunk_groups + 64) * 4;
+    const ScreenChunk ch = screen_chunk(cfg, kn.chunk_kb(NK > 16 ? 16384 : 3072));
     ScreenArgs a;
     a.F = Fs; a.Ft = F; a.info = info; a.glob = glob; a.perm = perm2; a.rowpos = rowpos; a.gmask = gmask;
-    a.blocks = d_blocks; a.sl = sl; a.cnt = cnt_out; a.flags = flags; a.g_state = g_state;
+    a.blocks = d_blocks; a.sl = t.sl; a.cnt = t.cnt; a.flags = t.flags; a.g_state = g_state;
     a.stats = ctx->d_stats; a.row_begin = 0; a.n_rows_all = n_rows;
-    a.k = k; a.dbg = (ctx->debug_flags & ~3) | env_int("WCX_PRE_DBG", 0); a.n_seg = 1; a.n_blocks = (int)blocks.size();
-    a.raw_est = raw_est;
+    a.k = k; a.dbg = ctx->debug_flags & ~DBG_SWEEP; a.n_seg = 1; a.n_blocks = (int)blocks.size();
+    a.raw_est = 1;
     a.gate = gate2;
     // (lists of at most 5 x 64 entries -- trigger + one group's appends -- take the short cut path of
     //  k_screen: five slices to load, select and write back instead of sixteen)
-    int trig_a = 4 * cut_r + 64;
-    if (trig_a > 256 && 2 * cut_r + 32 <= 256) trig_a = 256;
+    int trig_a = 4 * p.cut_r + 64;
+    if (trig_a > 256 && 2 * p.cut_r + 32 <= 256) trig_a = 256;
     if (trig_a > LIM) trig_a = LIM;
-    const int64_t g_end = P_s / GRr;
+    const int64_t g_end = P_s / (CTG * 32);
     bool first = true;
-    for (int64_t g0 = 0; g0 < g_end; g0 += chunk_groups) {
-      const int64_t g1 = g0 + chunk_groups < g_end ? g0 + chunk_groups : g_end;
+    for (int64_t g0 = 0; g0 < g_end; g0 += ch.groups) {
+      const int64_t g1 = g0 + ch.groups < g_end ? g0 + ch.groups : g_end;
       a.g_start = g0; a.g_count = (int)(g1 - g0);
-      a.cut_k = cut_r; a.cut_mode = 1; a.trig = trig_a; a.end_cut = g1 == g_end ? 1 : 0;
+      a.cut_k = p.cut_r; a.cut_mode = 1; a.trig = trig_a; a.end_cut = g1 == g_end ? 1 : 0;
       a.first = first ? 1 : 0;
       first = false;
-      const int e = screen_dispatch(cfg, a, (unsigned)blocks.size(), lds, st);
-      if (e < 0) {
-        wcx_set_error("screen kernel configuration nk=%d ctg=%d is not instantiated", cfg.nk, cfg.ctg);
-        return (int)WCX_ERR_UNSUPPORTED;
-      }
-      if (e != 0) {
-        wcx_set_error("screen kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        return (int)WCX_ERR_HIP;
-      }
+      rc = unit_status(launch_unit(screen_units, cfg, a, (unsigned)blocks.size(), ch.lds, st), "screen", cfg);
+      if (rc) return rc;
     }
-    k_sym_setup<<<gprep, NT, 0, st>>>(perm, info, glob, g_state, cnt_out, flags, Dest, tinfo, tmin, gate2);
+    k_sym_setup<<<(unsigned)((PB + NT - 1) / NT), NT, 0, st>>>(t.perm, info, glob, g_state, t.cnt, t.flags, Dest,
+                                                              tinfo, tmin, gate2);
     WCX_HIP(hipGetLastError());
     if (!use_hub) {
       rc = wcx_timer_end(ctx, "topk_pre");
       if (rc) return rc;
     }
-    sa.hub_appended = 0;
     rc = sweep_and_cut(gate2);
     if (rc) return rc;
   }
   rc = wcx_timer_end(ctx, "topk_screen");
   if (rc) return rc;
-  if (ctx->ev_after_sweep) WCX_HIP(hipEventRecord(ctx->ev_after_sweep, st));   // (wcx_sweep_event)
-  if (kick_at >= 1) {
-    const bool pending = ctx->rank_pending;
-    rc = wcx_aux_kick(ctx);
-    if (rc) return rc;
-    // (2: the refine waits for the ranking instead of running beside it -- an experiment switch)
-    if (kick_at == 2 && pending) WCX_HIP(hipStreamWaitEvent(st, ctx->ev_rank, 0));
-  }
-  rc = wcx_timer_begin(ctx, "topk_refine");
-  if (rc) return rc;
-  rc = wcx_refine_launch(ctx, Xr, S, Sp, tab, 0, n_rows, searched, sl, cnt_out, flags, perm, k, d_out_idx,
-                         d_out_dist, glob, cap2);
-  if (rc) return rc;
-  rc = wcx_timer_end(ctx, "topk_refine");
-  if (rc) return rc;
-  k_collect_redo<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(0, n_rows, searched, flags, tab, d_redo,
-                                                                   d_nredo, ctx->d_stats);
-  k_redo_plan<<<1, 64, 0, st>>>(tab, d_nredo, d_rtile);
-  k_redo_fill<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(0, n_rows, searched, flags, tab, d_nredo,
-                                                                d_rlist);
-  WCX_HIP(hipGetLastError());
-  rc = wcx_topk_exact_redo_launch(ctx, dXs, B, S, d_redo, d_nredo, d_rtile, d_nredo + 1, d_rlist,
-                                  base + o_rscr, 0, k, d_out_idx, d_out_dist);
-  if (rc) return rc;
-  return wcx_timer_end(ctx, "topk");
+  return finish_topk(ctx, t, 0, n_rows, kick_after_sweep(S), d_out_idx, d_out_dist);
 }
 
-int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
-                           const int64_t *chr_cum, int n_chr,
-                           const std::vector<TopkBlock> &exact_blocks, int64_t row_begin,
-                           int64_t n_rows, int k, int32_t *d_out_idx, double *d_out_dist) {
-  if (exact_blocks.empty()) return WCX_OK;
-  // One fp16 plane (its 2^-11 representation error only widens the shortlists by a few dozen
-  // entries; a hi+lo three-product form was measured 35 % slower end to end).  K = 16 NK holds the
-  // S data columns + 4 augmented columns (see k_screen_prep); NK is rounded up to an instantiated
-  // value.
-  static const int nk_list[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64};
-  int NK = 64;
-  for (int v : nk_list)
-    if (16 * v >= S + 4) { NK = v; break; }
-  // Kernel configuration: small K keeps TWO target tiles per wave in registers (every candidate
-  // fragment read from LDS feeds two MFMAs, one barrier per 4 NK MFMAs); large K uses eight
-  // waves per workgroup so that 256 targets share every staged candidate group.
-  ScreenCfg cfg;
-  cfg.nk = NK;
-  cfg.prof = (ctx->debug_flags & 4) && (NK == 7 || NK == 32) ? 1 : 0;
-  // Kernel configuration (measured on MI355X): 128 targets per workgroup; small K:
-  // 64 candidates per iteration, 3 waves per SIMD, LDS-DMA ring of 3; large K: 2 waves per SIMD
-  // (the targets' fragments alone take 4 NK registers), LDS-DMA double buffer.
-  // More than 508 samples (NK = 40 .. 64): the fragments of a wave's 32 targets alone take 160 .. 256
-  // registers -- one wave per SIMD on the unified VGPR + AGPR file, one workgroup per CU, a double
-  // buffer of 40 .. 64 KB groups in LDS.
-  if (NK <= 8) { cfg.ctg = 2; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 3; cfg.ring = 3; }
-  else if (NK <= 32) { cfg.ctg = NK <= 16 ? 2 : 1; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 2; cfg.ring = 2; }
-  else { cfg.ctg = 1; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 1; cfg.ring = 2; }
-  if (const char *e = getenv("WCX_SCREEN_TILE")) {     // testing / tuning: "ctg,tt,wpb,lb,ring"
-    int a = 0, b = 0, c = 0, d = 0, r = 0;
-    if (sscanf(e, "%d,%d,%d,%d,%d", &a, &b, &c, &d, &r) == 5) {
-      cfg.ctg = a; cfg.tt = b; cfg.wpb = c; cfg.lb = d; cfg.ring = r;
-    }
-  }
-  const int CTG = cfg.ctg;
-  const int TGT_WG = 32 * cfg.tt * cfg.wpb;
-  const int GRr = CTG * 32;
-  // Sampled pre-pass: the rows b = 0 (mod SF) are swept first (own region of the sweep order).
-  // (small problems with few samples -- the reference's default 100 kb bins: 27 k rows -- are bound by
-  //  their appends like every K < 256 sweep; without estimates the lists fill to the cut trigger first:
-  //  100 kb x 100 samples, sampling 0 / 4 / 8 / 16: appends per row 1 540 / 1 230 / 1 080 / 1 075, sweep
-  //  1.61 / 1.49 / 1.44 / 1.56 ms.  K >= 256 below 32 768 rows stays without: the symmetric path it would
-  //  open is sized and tested for the larger problems.)
-  int SF = (B >= 32768) ? 16 : ((B >= 8192 && NK < 16) ? 8 : 0);
-  SF = env_int("WCX_SCREEN_SAMPLE", SF);
-  if (SF < 2 || SF > 64) SF = 0;
-  int64_t n_s = SF ? (B + SF - 1) / SF : 0;                   // rows in the sample
-  int64_t P_s = (n_s + CT - 1) / CT * CT;                     // positions of the sample region
-  int64_t Bpad = P_s + ((B - n_s) + CT - 1) / CT * CT;
-  // regroup the searched row ranges into workgroups of <= TGT_WG rows (same chromosome)
-  auto make_blocks = [&](int max_rows) {
-    std::vector<ScreenBlock> out;
-    size_t i = 0;
-    while (i < exact_blocks.size()) {
-      ScreenBlock sb;
-      sb.row0 = exact_blocks[i].row0;
-      sb.nrows = exact_blocks[i].nrows;
-      sb.chr = 0;
-      for (int c = 0; c < n_chr; ++c)
-        if (chr_cum[c] == exact_blocks[i].ce && (c ? chr_cum[c - 1] : 0) == exact_blocks[i].cs) sb.chr = c;
-      sb.cs = exact_blocks[i].cs;
-      sb.ce = exact_blocks[i].ce;
-      size_t j = i + 1;
-      while (j < exact_blocks.size() && exact_blocks[j].cs == sb.cs &&
-             exact_blocks[j].row0 == sb.row0 + sb.nrows && sb.nrows + exact_blocks[j].nrows <= max_rows) {
-        sb.nrows += exact_blocks[j].nrows;
-        ++j;
-      }
-      out.push_back(sb);
-      i = j;
-    }
-    return out;
-  };
-  const std::vector<ScreenBlock> blocks = make_blocks(TGT_WG);
-  int64_t n_iter_groups = Bpad / GRr;
-  // Hub-count thresholds (decided further down, needed here for the segment rule): see use_hub1
-  const int need1 = (int)(1.18 * k) + 8;
-  const int hub_frac1 = env_int("WCX_HUB_FRAC", NK >= 16 ? 32 : 12);
-  int64_t hub_rows1 = hub_frac1 > 1 ? B / hub_frac1 : 0;
-  if (hub_rows1 < 8 * (int64_t)need1 + 512) hub_rows1 = 8 * (int64_t)need1 + 512;
-  auto hub1_possible = [&]() {
-    // (an explicit sampling rate / sample rank asks for the sampled pre-pass: tests of that path)
-    const int hub1_dflt = (getenv("WCX_SCREEN_SAMPLE") || getenv("WCX_SCREEN_CUT_R")) ? 0 : 1;
-    return env_int("WCX_SCREEN_HUB", hub1_dflt) != 0 && NK >= 5 && hub_frac1 > 1 && hub_rows1 * 6 <= B &&
-           cfg.wpb == 4 && cfg.ring >= 2;
-  };
-  // Candidate segments fill the chip when a row shard has few target blocks (multi-GPU builds)
-  // and even out the last round of workgroups: work items = blocks x segments.
-  int hw_cus = 256;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
-      hw_cus = prop.multiProcessorCount;
-  }
-  const int wg_per_cu = cfg.lb * 4 / cfg.wpb > 0 ? cfg.lb * 4 / cfg.wpb : 1;
-  const int slots = hw_cus * wg_per_cu;
-  // (measured on row shards of 1/2 .. 1/8 of the 15 kb problem, profiles/r02/shard_search_*.json: with
-  // the sampled pre-pass and 2-3 resident workgroups per CU the split no longer pays -- 1 segment
-  // is as fast or faster down to 178 blocks -- so it is off unless asked for)
-  int n_seg = 1;
-  // ... except for very small shards: the gonosomal passes search ~80-100 blocks of chrX / chrY
-  // rows on 512 slots; 1 / 2 / 4 segments: F pass 7.7 / 6.8 / 6.4 ms, M pass 8.8 / 7.6 / 7.4 ms
-  // (15 kb, 250 samples each, profiles/r03)
-  // Round 6 (hub-count thresholds: the segments' lists are short, the merge cheap): as many segments as fill
-  // ONE round of workgroup slots -- F pass, 77 blocks: 4 / 5 / 6 / 8 segments = screen 1.77 / 1.65 / 1.60 /
-  // 1.95 ms; M pass, 97 blocks: 4 / 5 / 6 = 2.13 / 1.95 / 2.50 (6 x 97 > 512 slots: a second round)
-  // (with hub-count thresholds already from half a round on: 100 kb x 100, 213 blocks on 768 slots, 1 / 2 / 3
-  //  segments = sweep 1.27 / 1.02 / 0.94 ms; with the sampled pre-pass segments made that shape slower, round 5)
-  const bool hub1_ahead = hub1_possible();
-  if ((int)blocks.size() * (hub1_ahead ? 2 : 4) <= slots) {
-    int fill = slots / (int)blocks.size();
-    if (fill > 8) fill = 8;
-    n_seg = env_int("WCX_SCREEN_SEGMENTS_SMALL", fill);
-  }
-  n_seg = env_int("WCX_SCREEN_SEGMENTS", n_seg);
-  if (n_seg < 1) n_seg = 1;
-  if (n_seg > 8) n_seg = 8;
-  // r = a rank in the sample that the k-th nearest of all candidates stays below with
-  // overwhelming probability (mean k/SF of the k nearest fall into the sample; + 10 % for the
-  // uneven share of the own chromosome, Poisson tail 1e-6 per row): the estimate admits ~r SF
-  // candidates; a row whose estimate fails costs ~0.1 ms in the device-wide redo.
-  // WCX_EST_MARGIN=1: the estimate carries the filter margin like a proven threshold (round 2-4).
-  // Default: the raw r-th sample value, r chosen for the rank the final cut needs below the estimate --
-  // that of the k-th neighbour's filter bound: 1.135 k entries survive the final cut at 15 kb (S = 100
-  // and 500), allowed for with 1.18 k.
-  const int raw_est = env_int("WCX_EST_MARGIN", 0) ? 0 : 1;
-  auto sample_rank = [&](int nseg) {
-    if (!SF) return 0;
-    // smallest r with P(Poisson(lambda) >= r) <= 1e-6 / n_seg,  lambda = 1.1 k / (SF n_seg)
-    const double lambda = 1.1 * (raw_est ? 1.18 : 1.0) * (double)k / ((double)SF * nseg);
-    const double target = 1e-6 / nseg;
-    double term = exp(-lambda), cdf = 0.0;   // term = P(X = i)
-    int i = 0;
-    for (; i < 4 * k; ++i) {
-      if (1.0 - cdf <= target && (double)i > lambda) break;
-      cdf += term;
-      term *= lambda / (double)(i + 1);
-    }
-    int r = i + 1;
-    // the sample must hold several times r candidates and r must be well below k
-    if (r * 2 > k || P_s / nseg < 16 * (int64_t)r) r = 0;
-    // testing: a deliberately unsafe rank makes estimates fail, which the final cut must detect
-    // (rows go to the exact kernel; results stay identical)
-    const int forced = env_int("WCX_SCREEN_CUT_R", 0);
-    if (forced > 0 && forced < k) r = forced;
-    return r;
-  };
-  int cut_r = sample_rank(n_seg);
-  // All rows searched against all rows with a sampled pre-pass available: the symmetric sweep
-  // (half the matrix work; screen_sym.h).  WCX_SCREEN_SYM=0 keeps the one-directional sweep.
-  {
-    int64_t covered = 0;
-    for (const ScreenBlock &sb : blocks) covered += sb.nrows;
-    const int cut_r1 = sample_rank(1);     // (the symmetric sweep has no candidate segments)
-    // WCX_SCREEN_SYM: 0 = never, 1 = where it pays (default), 2 = whenever possible (tests).  Small K
-    // is bound by the appends, not by the matrix pipe, and the symmetric sweep's hit path is the dearer
-    // one (15 kb, symmetric against one-directional: K = 112: 13.9 / 11.3 ms; K = 192: 17.3 / 15.6; K = 256: 17.4 /
-    // 20.0; K = 512: 23.4 / 31.5)
-    const int sym_mode = env_int("WCX_SCREEN_SYM", 1);
-    if (cut_r1 && row_begin == 0 && n_rows == B && covered == B && cfg.tt == 1 && cfg.wpb == 4 &&
-        cfg.ring >= 2 && (sym_mode == 2 || (sym_mode == 1 && NK >= 16)))
-      return screen_sym_path(ctx, dXs, B, S, chr_cum, n_chr, blocks, cfg, SF, cut_r1, raw_est, slots, k,
-                             d_out_idx, d_out_dist);
-  }
-  // the one-directional sweep keeps k + its filter margin inside shortlists of CAP entries: a larger
-  // refsize of a row shard / gonosomal pass goes to the exact kernel
-  if (k > KMAX_ONE_DIR)
-    return wcx_topk_exact_launch(ctx, dXs, B, S, exact_blocks, row_begin, n_rows, k, d_out_idx, d_out_dist);
-  // Thresholds from COUNTS over the low-norm rows instead of the sampled pre-pass (screen_hub1.h; round 6:
-  // what round 5 gave the symmetric sweep, for row shards, gonosomal passes and K < 256).  The head region
-  // of the sweep order is then the hub region -- 1 / WCX_HUB_FRAC of the rows, at least 8 x the entries
-  // wanted below an estimate + the 512 candidates of the moment phase -- whose size only the device knows:
-  // the host sizes everything for the bound (one more group of padding at most).  WCX_SCREEN_HUB=0: off.
-  const bool use_hub1 = hub1_ahead && k <= KMAX_ONE_DIR;
-  // (the count pass always runs 128-row blocks in its own configuration; a sweep with two target tiles per
-  //  wave -- WCX_SCREEN_TILE, experiments -- gets its own block list)
-  std::vector<ScreenBlock> hub_blocks;
-  if (use_hub1 && TGT_WG != 128) hub_blocks = make_blocks(128);
-  if (use_hub1) {
-    SF = 0;
-    n_s = 0;
-    P_s = 0;
-    Bpad = (B + CT - 1) / CT * CT + CT;
-    n_iter_groups = Bpad / GRr;
-    cut_r = 0;
-  }
-  // scratch layout
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_glob = carve(sizeof(ScreenGlobals));
-  const size_t o_mean = carve((size_t)S * 8 * (3 + 2 * CSPLIT));   // mean | min | max | partial sums | partial counts
-  const int Sp = row_pitch(S);
-  const size_t o_xr = carve((size_t)B * Sp * 8 + 256);   // + slack: refine loads whole 128-B chunks
-  const size_t o_F = carve((size_t)Bpad * NK * 32);  // Bpad/32 tiles * NK * 1 KiB
-  const size_t o_info = carve((size_t)Bpad * sizeof(RowInfo));
+// The one-directional sweep of the rows [row_begin, row_begin + n_rows) against all rows: an optional
+// head pass for thresholds (hub counts or the sampled pre-pass), then k_screen over the chunks of
+// the sweep order
+static int screen_one_dir_path(wcx_ctx *ctx, const Knobs &kn, const ScreenPlan &p, const double *dXs, int64_t B,
+                               int S, const int64_t *chr_cum, int n_chr, int64_t row_begin, int64_t n_rows, int k,
+                               int32_t *d_out_idx, double *d_out_dist) {
+  const ScreenCfg &cfg = p.cfg;
+  const std::vector<ScreenBlock> &blocks = p.blocks, &hub_blocks = p.hub_blocks;
+  const int NK = cfg.nk, GRr = cfg.ctg * 32, SF = p.SF, n_seg = p.n_seg, cut_r = p.cut_r;
+  const bool use_hub1 = p.use_hub1;
+  const int64_t n_s = SF ? (B + SF - 1) / SF : 0;                   // rows in the sample
+  const int64_t P_s = (n_s + CT - 1) / CT * CT;                     // positions of the sample region
+  // (hub counts: the hub region's size only the device knows -- one more group of padding at most)
+  const int64_t Bpad = P_s + ((B - n_s) + CT - 1) / CT * CT + (use_hub1 ? CT : 0);
+  const int64_t n_iter_groups = Bpad / GRr;
   const int64_t n_groups = Bpad / CT;
-  const size_t o_perm = carve((size_t)Bpad * 4);
-  const size_t o_rpos = carve((size_t)B * 4);
-  const size_t o_rbit = carve((size_t)B * 4);
-  const size_t o_rfin = carve(use_hub1 ? (size_t)B * 4 : 0);
-  const size_t o_hubh = carve(use_hub1 ? (size_t)HUB_BINS * 4 : 0);
-  const size_t o_rchr = carve((size_t)B * 4);
-  const size_t o_rkey = carve((size_t)B * 4);
-  const size_t o_cell = carve((size_t)2 * NCELL * 4);
-  const size_t o_curs = carve((size_t)2 * NCELL * 4);
-  const size_t o_gmsk = carve((size_t)n_groups * 4);
-  const size_t o_sl = carve((size_t)n_seg * n_rows * CAP * 8);
-  const size_t o_cnt = carve((size_t)n_seg * n_rows * 4);
-  const size_t o_gst = carve((size_t)n_seg * n_rows * 4);
-  const size_t o_flag = carve((size_t)n_seg * n_rows * 4);
-  const size_t o_srch = carve((size_t)n_rows);
-  const size_t o_blk = carve(blocks.size() * sizeof(ScreenBlock));
-  const size_t o_hblk = carve(hub_blocks.size() * sizeof(ScreenBlock));
-  const size_t o_redo = carve((size_t)n_rows * sizeof(TopkBlock));
-  const size_t o_nredo = carve(512);                                   // counters, see k_collect_redo
-  const size_t o_rtile = carve(((size_t)n_rows / 64 + 64) * sizeof(TopkBlock));
-  const size_t o_rlist = carve((size_t)n_rows * 4);
-  const size_t o_rscr = carve(wcx_topk_redo_scratch_bytes(k, B));
+  const int Sp = row_pitch(S);
+  TopkTail t;
+  ScreenGlobals *glob;
+  double *cmean;
+  half8 *F;
+  RowInfo *info;
+  int *rowpos, *hubhist, *rchr, *rkey, *cellcnt, *cursor;
+  unsigned int *rbits, *rfine, *gmask;
+  float *g_state;
+  ScreenBlock *d_blocks, *d_hblocks;
+  auto layout = [&](uintptr_t base) {
+    Carve take{base};
+    take(glob, sizeof(ScreenGlobals));
+    take(cmean, (size_t)S * 8 * (3 + 2 * CSPLIT));
+    take(t.Xr, (size_t)B * Sp * 8 + 256);           // + slack: refine loads whole 128-B chunks
+    take(F, (size_t)Bpad * NK * 32);                 // Bpad/32 tiles * NK * 1 KiB
+    take(info, (size_t)Bpad * sizeof(RowInfo));
+    take(t.perm, (size_t)Bpad * 4);
+    take(rowpos, (size_t)B * 4);
+    take(rbits, (size_t)B * 4);
+    take(rfine, use_hub1 ? (size_t)B * 4 : 0);
+    take(hubhist, use_hub1 ? (size_t)HUB_BINS * 4 : 0);
+    take(rchr, (size_t)B * 4);
+    take(rkey, (size_t)B * 4);
+    take(cellcnt, (size_t)2 * NCELL * 4);
+    take(cursor, (size_t)2 * NCELL * 4);
+    take(gmask, (size_t)n_groups * 4);
+    take(t.sl, (size_t)n_seg * n_rows * CAP * 8);
+    take(t.cnt, (size_t)n_seg * n_rows * 4);
+    take(g_state, (size_t)n_seg * n_rows * 4);
+    take(t.flags, (size_t)n_seg * n_rows * 4);
+    take(t.searched, (size_t)n_rows);
+    take(d_blocks, blocks.size() * sizeof(ScreenBlock));
+    take(d_hblocks, hub_blocks.size() * sizeof(ScreenBlock));
+    take(t.d_redo, (size_t)n_rows * sizeof(TopkBlock));
+    take(t.d_nredo, 512);                            // counters, see k_collect_redo
+    take(t.d_rtile, ((size_t)n_rows / 64 + 64) * sizeof(TopkBlock));
+    take(t.d_rlist, (size_t)n_rows * 4);
+    take(t.rscr, wcx_topk_redo_scratch_bytes(k, B));
+    return (size_t)(take.at - base);
+  };
   void *scr = nullptr;
-  int rc = wcx_scratch(ctx, off, &scr);
+  int rc = wcx_scratch(ctx, layout(0), &scr);
   if (rc) return rc;
-  char *base = reinterpret_cast<char *>(scr);
-  ScreenGlobals *glob = reinterpret_cast<ScreenGlobals *>(base + o_glob);
-  double *cmean = reinterpret_cast<double *>(base + o_mean);
-  double *Xr = reinterpret_cast<double *>(base + o_xr);
-  half8 *F = reinterpret_cast<half8 *>(base + o_F);
-  RowInfo *info = reinterpret_cast<RowInfo *>(base + o_info);
-  int *perm = reinterpret_cast<int *>(base + o_perm);
-  int *rowpos = reinterpret_cast<int *>(base + o_rpos);
-  unsigned int *rbits = reinterpret_cast<unsigned int *>(base + o_rbit);
-  int *rchr = reinterpret_cast<int *>(base + o_rchr);
-  int *rkey = reinterpret_cast<int *>(base + o_rkey);
-  int *cellcnt = reinterpret_cast<int *>(base + o_cell);
-  int *cursor = reinterpret_cast<int *>(base + o_curs);
-  unsigned int *gmask = reinterpret_cast<unsigned int *>(base + o_gmsk);
-  uint2 *sl = reinterpret_cast<uint2 *>(base + o_sl);
-  int *cnt_out = reinterpret_cast<int *>(base + o_cnt);
-  float *g_state = reinterpret_cast<float *>(base + o_gst);
-  unsigned int *flags = reinterpret_cast<unsigned int *>(base + o_flag);
-  unsigned char *searched = reinterpret_cast<unsigned char *>(base + o_srch);
-  ScreenBlock *d_blocks = reinterpret_cast<ScreenBlock *>(base + o_blk);
-  TopkBlock *d_redo = reinterpret_cast<TopkBlock *>(base + o_redo);
-  unsigned int *d_nredo = reinterpret_cast<unsigned int *>(base + o_nredo);
-  TopkBlock *d_rtile = reinterpret_cast<TopkBlock *>(base + o_rtile);
-  int32_t *d_rlist = reinterpret_cast<int32_t *>(base + o_rlist);
-
+  layout(reinterpret_cast<uintptr_t>(scr));
+  t.dXs = dXs; t.B = B; t.S = S; t.Sp = Sp; t.k = k; t.cap2 = CAP; t.glob = glob;
   hipStream_t st = ctx->stream;
   WCX_HIP(hipMemsetAsync(glob, 0, sizeof(ScreenGlobals), st));
-  WCX_HIP(hipMemsetAsync(cnt_out, 0, (size_t)n_seg * n_rows * 4, st));
-  WCX_HIP(hipMemsetAsync(flags, 0, (size_t)n_seg * n_rows * 4, st));
-  WCX_HIP(hipMemsetAsync(searched, 0, (size_t)n_rows, st));
-  WCX_HIP(hipMemsetAsync(d_nredo, 0, 512, st));
+  WCX_HIP(hipMemsetAsync(t.cnt, 0, (size_t)n_seg * n_rows * 4, st));
+  WCX_HIP(hipMemsetAsync(t.flags, 0, (size_t)n_seg * n_rows * 4, st));
+  WCX_HIP(hipMemsetAsync(t.searched, 0, (size_t)n_rows, st));
+  WCX_HIP(hipMemsetAsync(t.d_nredo, 0, 512, st));
   WCX_HIP(hipMemsetAsync(ctx->d_stats, 0, 256, st));
   rc = wcx_upload_small(ctx, d_blocks, blocks.data(), blocks.size() * sizeof(ScreenBlock));
   if (rc) return rc;
-  k_mark<<<(unsigned)blocks.size(), 256, 0, st>>>(searched, d_blocks, row_begin);
+  k_mark<<<(unsigned)blocks.size(), 256, 0, st>>>(t.searched, d_blocks, row_begin);
 
   rc = wcx_timer_begin(ctx, "topk");
   if (rc) return rc;
   rc = wcx_timer_begin(ctx, "topk_prep");
   if (rc) return rc;
-  unsigned long long *cmin = reinterpret_cast<unsigned long long *>(cmean + S);
-  unsigned long long *cmax = cmin + S;
-  double *psum = cmean + 3 * S, *pcnt = psum + (size_t)S * CSPLIT;
-  WCX_HIP(hipMemsetAsync(cmin, 0xff, (size_t)S * 8, st));
-  WCX_HIP(hipMemsetAsync(cmax, 0, (size_t)S * 8, st));
-  k_col_sum<<<dim3((unsigned)S, CSPLIT), NT, 0, st>>>(dXs, B, psum, pcnt, cmin, cmax);
-  k_col_stats<<<(unsigned)((S + 63) / 64), 64, 0, st>>>(S, psum, pcnt, cmin, cmax, cmean, glob);
-  ChrTab tab;
-  tab.n_chr = n_chr;
-  for (int c = 0; c < 32; ++c) tab.cum[c] = c < n_chr ? chr_cum[c] : B;
+  rc = col_stats(dXs, B, S, cmean, glob, chr_cum, n_chr, t.tab, st);
+  if (rc) return rc;
+  const ChrTab &tab = t.tab;
   {
     const unsigned gb = (unsigned)((B + NT - 1) / NT);
     const unsigned gtn = (unsigned)((B + 31) / 32);
     WCX_HIP(hipMemsetAsync(cellcnt, 0, (size_t)2 * NCELL * 4, st));
-    WCX_HIP(hipMemsetAsync(perm, 0xff, (size_t)Bpad * 4, st));
+    WCX_HIP(hipMemsetAsync(t.perm, 0xff, (size_t)Bpad * 4, st));
     if (use_hub1) {
-      unsigned int *rfine = reinterpret_cast<unsigned int *>(base + o_rfin);
-      int *hubhist = reinterpret_cast<int *>(base + o_hubh);
       WCX_HIP(hipMemsetAsync(hubhist, 0, (size_t)HUB_BINS * 4, st));
-      k_transpose_norm<<<gtn, 256, 0, st>>>(dXs, B, S, Sp, Xr, cmean, tab, glob, rbits, rchr, rfine, hubhist);
-      k_hub_cut<<<1, 1024, 0, st>>>(hubhist, (int)hub_rows1, glob);
+      k_transpose_norm<<<gtn, 256, 0, st>>>(dXs, B, S, Sp, t.Xr, cmean, tab, glob, rbits, rchr, rfine, hubhist);
+      k_hub_cut<<<1, 1024, 0, st>>>(hubhist, (int)p.hub_rows, glob);
       k_row_hist<<<gb, NT, 0, st>>>(rbits, rchr, B, 0, 0, glob, rkey, cellcnt, nullptr, rfine);
       k_scan_cells<<<1, 1024, 0, st>>>(cellcnt, cursor, 0, nullptr, glob);
     } else {
-      k_transpose_norm<<<gtn, 256, 0, st>>>(dXs, B, S, Sp, Xr, cmean, tab, glob, rbits, rchr, nullptr, nullptr);
+      k_transpose_norm<<<gtn, 256, 0, st>>>(dXs, B, S, Sp, t.Xr, cmean, tab, glob, rbits, rchr, nullptr, nullptr);
       k_row_hist<<<gb, NT, 0, st>>>(rbits, rchr, B, SF, n_seg > 1 ? 1 : 0, glob, rkey, cellcnt);
       k_scan_cells<<<1, 1024, 0, st>>>(cellcnt, cursor, (int)(P_s - n_s));
     }
-    k_scatter<<<gb, NT, 0, st>>>(rkey, B, cursor, perm, rowpos);
-    k_group_mask<<<(unsigned)((n_groups + NT - 1) / NT), NT, 0, st>>>(perm, rchr, n_groups, gmask);
+    k_scatter<<<gb, NT, 0, st>>>(rkey, B, cursor, t.perm, rowpos);
+    k_group_mask<<<(unsigned)((n_groups + NT - 1) / NT), NT, 0, st>>>(t.perm, rchr, n_groups, gmask);
   }
-  const unsigned gprep = (unsigned)((Bpad + 31) / 32);              // one workgroup per 32-row tile
-  switch (NK) {
-#define WCX_PREP_CASE(N) case N: k_screen_prep<N><<<gprep, NT, 0, st>>>(Xr, Bpad, S, Sp, cmean, perm, glob, F, info); break;
-    WCX_PREP_CASE(1) WCX_PREP_CASE(2) WCX_PREP_CASE(3) WCX_PREP_CASE(4) WCX_PREP_CASE(5)
-    WCX_PREP_CASE(6) WCX_PREP_CASE(7) WCX_PREP_CASE(8) WCX_PREP_CASE(10) WCX_PREP_CASE(12)
-    WCX_PREP_CASE(14) WCX_PREP_CASE(16) WCX_PREP_CASE(20) WCX_PREP_CASE(24) WCX_PREP_CASE(28)
-    WCX_PREP_CASE(40) WCX_PREP_CASE(48) WCX_PREP_CASE(56) WCX_PREP_CASE(64)
-    default: k_screen_prep<32><<<gprep, NT, 0, st>>>(Xr, Bpad, S, Sp, cmean, perm, glob, F, info); break;
-#undef WCX_PREP_CASE
-  }
-  WCX_HIP(hipGetLastError());
-  rc = wcx_timer_end(ctx, "topk_prep");
-  if (rc) return rc;
-  // pending null-sample ranking (auxiliary stream): 0 = start beside the sweep, 1 = beside the
-  // refine.  Measured (15 kb, S = 500 / 100): the step takes the same time either way (73.2 / 73.1 ms;
-  // serial: 73.6), but beside the sweep the sort's HBM streaming costs the power-limited MFMA loop
-  // 6 % (33.4 vs 31.6 ms), beside the refine it costs the refine 2 ms -- so it goes there.
-  // (a short refine -- few samples -- cannot hide the 2.4 ms sort: S = 100 is 0.8 ms faster with
-  // the sort beside the sweep)
-  const int kick_at = env_int("WCX_RANK_KICK", S >= 256 ? 1 : 0);
-  if (kick_at == 0) {
-    rc = wcx_aux_kick(ctx);
-    if (rc) return rc;
-  }
-  rc = wcx_timer_begin(ctx, "topk_screen");
+  screen_prep(NK, t.Xr, Bpad, S, Sp, cmean, t.perm, glob, F, info, nullptr, st);
+  rc = end_prep(ctx, S);
   if (rc) return rc;
 
   // candidate chunk per launch: a few MB of fragments (3 MB fits the 4 MB XCD L2)
-  const int64_t group_bytes = (int64_t)GRr * NK * 32;
   // (every launch costs ~30 us of prologue per round of workgroups -- target fragments, visit
   // list --, so large K, whose groups are big, takes bigger chunks: L2 misses go to the MALL.
   // Every launch also re-reads the 128 KB of target fragments of each of its workgroups, which is
@@ -1920,53 +1936,39 @@ int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
   // (rocprofv3 FETCH_SIZE x 2, scripts/sweep_chunk_traffic.sh): 2 / 3 / 4 / 8 / 16 / 32 / 64 / 128 MB
   // -> 59 / 44 / 36 / 24.5 / 19.8 / 25 / 45 / 63 GB, sweep 32.7 / 31.8 / 31.5 / 31.3 / 31.2 / 32.5 /
   // 33.7 / 42.7 ms: beyond 16 MB the workgroups of a launch drift apart and stop sharing lines)
-  int64_t chunk_groups = ((int64_t)env_int("WCX_SCREEN_CHUNK_KB", NK > 16 ? 16384 : 3072) << 10) / group_bytes;
   // (small shards swept in candidate segments -- the gonosomal passes: ~300 workgroups, less than one
   // round -- have no tail to hide and no L2 to share in step; their launches only cost: 3 / 6 / 12 /
   // 24 MB chunks: F pass screen 4.56 / 3.73 / 3.43 / 3.22 ms, M pass 5.33 / 4.87 / 4.34 / 4.16 ms)
-  if (n_seg > 1) chunk_groups = ((int64_t)env_int("WCX_SCREEN_CHUNK_KB_SMALL", 24576) << 10) / group_bytes;
-  if (chunk_groups < 16) chunk_groups = 16;
-  if (chunk_groups > 4096) chunk_groups = 4096;
-  const size_t lds = (size_t)(cfg.ring >= 2 ? cfg.ring : 2) * (size_t)(CTG * NK * 64) * 16 +
-                     (size_t)(chunk_groups + 64) * 4;   // + the chunk's visit list
+  const ScreenChunk ch =
+      screen_chunk(cfg, n_seg > 1 ? kn.chunk_kb_small(24576) : kn.chunk_kb(NK > 16 ? 16384 : 3072));
   ScreenArgs a;
-  a.F = F; a.Ft = F; a.info = info; a.glob = glob; a.perm = perm; a.rowpos = rowpos; a.gmask = gmask;
-  a.blocks = d_blocks; a.sl = sl; a.cnt = cnt_out; a.flags = flags; a.g_state = g_state;
+  a.F = F; a.Ft = F; a.info = info; a.glob = glob; a.perm = t.perm; a.rowpos = rowpos; a.gmask = gmask;
+  a.blocks = d_blocks; a.sl = t.sl; a.cnt = t.cnt; a.flags = t.flags; a.g_state = g_state;
   a.stats = ctx->d_stats; a.row_begin = row_begin; a.n_rows_all = n_rows;
   a.k = k; a.dbg = ctx->debug_flags; a.n_seg = n_seg; a.n_blocks = (int)blocks.size();
-  a.raw_est = raw_est;
-  // Every chunk launch ends with a partly filled last round of workgroups (1423 blocks on 512
-  // slots = 2.78 rounds at 15 kb).  With more than one round of blocks the target blocks are split
-  // in two halves that sweep the same chunks on two streams: when one half's launch drains, the
-  // other half's workgroups fill the freed slots -- the per-launch tails overlap instead of adding
-  // up.  (Blocks are independent: all per-target state is addressed through ScreenBlock::row0.)
+  a.raw_est = 1;
   if (use_hub1) {
     rc = wcx_timer_begin(ctx, "topk_pre");
     if (rc) return rc;
     // its own configuration (the default rule for this K), whatever tile the sweep was asked to use
-    ScreenCfg hc;
-    hc.nk = NK; hc.tt = 1; hc.wpb = 4; hc.prof = 0;
-    if (NK <= 8) { hc.ctg = 2; hc.lb = 3; hc.ring = 3; }
-    else if (NK <= 32) { hc.ctg = NK <= 16 ? 2 : 1; hc.lb = 2; hc.ring = 2; }
-    else { hc.ctg = 1; hc.lb = 1; hc.ring = 2; }
-    const ScreenBlock *d_hblocks = d_blocks;
+    const ScreenCfg hc = default_cfg(NK);
     size_t n_hblocks = blocks.size();
     if (!hub_blocks.empty()) {
-      ScreenBlock *dh = reinterpret_cast<ScreenBlock *>(base + o_hblk);
-      rc = wcx_upload_small(ctx, dh, hub_blocks.data(), hub_blocks.size() * sizeof(ScreenBlock));
+      rc = wcx_upload_small(ctx, d_hblocks, hub_blocks.data(), hub_blocks.size() * sizeof(ScreenBlock));
       if (rc) return rc;
-      d_hblocks = dh;
       n_hblocks = hub_blocks.size();
+    } else {
+      d_hblocks = d_blocks;
     }
     Hub1Args ha;
-    ha.F = F; ha.glob = glob; ha.perm = perm; ha.rowpos = rowpos; ha.gmask = gmask; ha.blocks = d_hblocks;
-    ha.g_state = g_state; ha.cnt = cnt_out; ha.stats = ctx->d_stats; ha.row_begin = row_begin;
-    ha.n_rows_all = n_rows; ha.n_seg = n_seg; ha.need = env_int("WCX_HUB_TEST_FAIL", 0) ? (1 << 28) : need1;
-    ha.n1 = env_int("WCX_HUB_N1", 16);
+    ha.F = F; ha.glob = glob; ha.perm = t.perm; ha.rowpos = rowpos; ha.gmask = gmask; ha.blocks = d_hblocks;
+    ha.g_state = g_state; ha.cnt = t.cnt; ha.stats = ctx->d_stats; ha.row_begin = row_begin;
+    ha.n_rows_all = n_rows; ha.n_seg = n_seg; ha.need = p.hub_need;
+    ha.n1 = kn.hub_n1(16);
     // the visit list holds the hub groups: room for twice the rows asked for (the quantile takes a whole
     // histogram bin); a bigger region is cut off there by the kernel
     const int hGR = hc.ctg * 32;
-    int64_t cap_g = (hub_rows1 * 2 + hGR - 1) / hGR + 2;
+    int64_t cap_g = (p.hub_rows * 2 + hGR - 1) / hGR + 2;
     if (cap_g > Bpad / hGR) cap_g = Bpad / hGR;
     if (cap_g > 8192) cap_g = 8192;
     ha.glist_cap = (int)cap_g + 64;
@@ -1975,26 +1977,19 @@ int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
     //  in-sweep cut -- but cost the count pass 2 x 8 vector instructions per output, which at K <= 128 and
     //  more than a round of workgroups is what bounds it: 15 kb x 100: 4 / 8 trials = pass 1.24 / 1.91 ms,
     //  sweep total 11.59 / 11.89; 100 kb x 100, 213 workgroups: 1.63 / 1.36 ms)
-    const int trials = env_int("WCX_HUB1_TRIALS", (NK >= 16 || (int)n_hblocks <= hw_cus * hc.lb) ? 8 : 4);
-    int e = wcx_hub1_launch_k1(NK, hc.ctg, hc.lb, hc.ring, trials, ha, (unsigned)n_hblocks, lds_h, st);
-    if (e < 0) e = wcx_hub1_launch_k2(NK, hc.ctg, hc.lb, hc.ring, trials, ha, (unsigned)n_hblocks, lds_h, st);
-    if (e < 0) e = wcx_hub1_launch_k3(NK, hc.ctg, hc.lb, hc.ring, trials, ha, (unsigned)n_hblocks, lds_h, st);
-    if (e < 0) e = wcx_hub1_launch_k4(NK, hc.ctg, hc.lb, hc.ring, trials, ha, (unsigned)n_hblocks, lds_h, st);
-    if (e < 0) {
-      wcx_set_error("hub-count kernel (one-directional) nk=%d ctg=%d lb=%d ring=%d trials=%d is not instantiated",
-                    NK, hc.ctg, hc.lb, hc.ring, trials);
-      return (int)WCX_ERR_UNSUPPORTED;
-    }
-    if (e != 0) {
-      wcx_set_error("hub-count kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      return (int)WCX_ERR_HIP;
-    }
+    const int trials = kn.hub1_trials((NK >= 16 || (int)n_hblocks <= p.hw_cus * hc.lb) ? 8 : 4);
+    rc = unit_status(launch_unit(hub1_units, NK, hc.ctg, hc.lb, hc.ring, trials, ha, (unsigned)n_hblocks, lds_h, st),
+                     "hub-count (one-directional)", hc, trials);
+    if (rc) return rc;
     rc = wcx_timer_end(ctx, "topk_pre");
     if (rc) return rc;
   }
-  int n_streams = ((int)blocks.size() > slots && n_seg == 1) ? 2 : 1;
-  n_streams = env_int("WCX_SCREEN_STREAMS", n_streams);
-  if (n_streams != 2 || n_seg != 1 || blocks.size() < 2) n_streams = 1;
+  // Every chunk launch ends with a partly filled last round of workgroups (1423 blocks on 512
+  // slots = 2.78 rounds at 15 kb).  With more than one round of blocks the target blocks are split
+  // in two halves that sweep the same chunks on two streams: when one half's launch drains, the
+  // other half's workgroups fill the freed slots -- the per-launch tails overlap instead of adding
+  // up.  (Blocks are independent: all per-target state is addressed through ScreenBlock::row0.)
+  const int n_streams = ((int)blocks.size() > p.slots && n_seg == 1) ? 2 : 1;
   hipStream_t st2 = st;
   if (n_streams == 2) {
     if (!ctx->sweep_stream) {
@@ -2016,46 +2011,38 @@ int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
     for (int h = 0; h < n_streams; ++h) {
       a.blocks = d_blocks + (h ? half0 : 0);
       a.n_blocks = h ? (int)blocks.size() - half0 : half0;
-      const int e = screen_dispatch(cfg, a, (unsigned)(a.n_blocks * n_seg), lds, h ? st2 : st);
-      if (e < 0) {
-        wcx_set_error("screen kernel configuration nk=%d ctg=%d tt=%d wpb=%d lb=%d ring=%d is not instantiated",
-                      cfg.nk, cfg.ctg, cfg.tt, cfg.wpb, cfg.lb, cfg.ring);
-        return (int)WCX_ERR_UNSUPPORTED;
-      }
-      if (e != 0) {
-        wcx_set_error("screen kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        return (int)WCX_ERR_HIP;
-      }
+      const int e = unit_status(launch_unit(screen_units, cfg, a, (unsigned)(a.n_blocks * n_seg), ch.lds,
+                                            h ? st2 : st), "screen", cfg);
+      if (e) return e;
     }
     return (int)WCX_OK;
   };
-  const int trig_main = (ctx->debug_flags >> 8) ? (ctx->debug_flags >> 8) : LIM;   // (diagnostics)
+  const int trig_main = (ctx->debug_flags >> DBG_TRIG_SHIFT) ? (ctx->debug_flags >> DBG_TRIG_SHIFT) : LIM;
   int64_t g_main = 0;
   if (cut_r) {   // sampled pre-pass: a streaming top-r over the sample region
     g_main = P_s / GRr;
     int trig_a = n_seg > 1 ? 2 * cut_r + 32 : 4 * cut_r + 64;   // (random order: cut more often)
     if (trig_a > LIM) trig_a = LIM;
-    for (int64_t g0 = 0; g0 < g_main; g0 += chunk_groups) {
-      const int64_t g1 = g0 + chunk_groups < g_main ? g0 + chunk_groups : g_main;
+    for (int64_t g0 = 0; g0 < g_main; g0 += ch.groups) {
+      const int64_t g1 = g0 + ch.groups < g_main ? g0 + ch.groups : g_main;
       rc = launch(g0, g1, cut_r, 1, trig_a, g1 == g_main ? 1 : 0);
       if (rc) return rc;
     }
     if (n_seg > 1)
-      k_share_thresholds<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(n_rows, n_seg, searched,
-                                                                            g_state, cnt_out);
+      k_share_thresholds<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(n_rows, n_seg, t.searched,
+                                                                            g_state, t.cnt);
   }
-  for (int64_t g0 = g_main; g0 < n_iter_groups; g0 += chunk_groups) {
-    const int64_t g1 = g0 + chunk_groups < n_iter_groups ? g0 + chunk_groups : n_iter_groups;
+  for (int64_t g0 = g_main; g0 < n_iter_groups; g0 += ch.groups) {
+    const int64_t g1 = g0 + ch.groups < n_iter_groups ? g0 + ch.groups : n_iter_groups;
     rc = launch(g0, g1, k, 0, trig_main, g1 == n_iter_groups ? 2 : 0);
     if (rc) return rc;
   }
   if (n_seg > 1) {
-    const float gamma = (float)(16 * NK + 12) * 1.1920929e-7f;
     const unsigned gm = (unsigned)((n_rows + 3) / 4 < 65536 ? (n_rows + 3) / 4 : 65536);
     for (int step = 1; step < n_seg; step *= 2) {
       const unsigned pairs = (unsigned)((n_seg - step + 2 * step - 1) / (2 * step));
-      k_merge_segments<<<dim3(gm, pairs), NT, 0, st>>>(info, glob, rowpos, row_begin, n_rows, searched, sl,
-                                                       cnt_out, flags, g_state, step, n_seg, k, gamma,
+      k_merge_segments<<<dim3(gm, pairs), NT, 0, st>>>(info, glob, rowpos, row_begin, n_rows, t.searched, t.sl,
+                                                       t.cnt, t.flags, g_state, step, n_seg, k, screen_gamma(NK),
                                                        step * 2 >= n_seg ? 1 : 0);
     }
   }
@@ -2066,33 +2053,25 @@ int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
   WCX_HIP(hipGetLastError());
   rc = wcx_timer_end(ctx, "topk_screen");
   if (rc) return rc;
-  if (ctx->ev_after_sweep) WCX_HIP(hipEventRecord(ctx->ev_after_sweep, st));   // (wcx_sweep_event)
-  if (kick_at >= 1) {
-    const bool pending = ctx->rank_pending;
-    rc = wcx_aux_kick(ctx);
-    if (rc) return rc;
-    // (2: the refine waits for the ranking instead of running beside it -- an experiment switch)
-    if (kick_at == 2 && pending) WCX_HIP(hipStreamWaitEvent(st, ctx->ev_rank, 0));
+  return finish_topk(ctx, t, row_begin, n_rows, kick_after_sweep(S), d_out_idx, d_out_dist);
+}
+
+int wcx_topk_screen_launch(wcx_ctx *ctx, const double *dXs, int64_t B, int S,
+                           const int64_t *chr_cum, int n_chr,
+                           const std::vector<TopkBlock> &exact_blocks, int64_t row_begin,
+                           int64_t n_rows, int k, int32_t *d_out_idx, double *d_out_dist) {
+  if (exact_blocks.empty()) return WCX_OK;
+  const Knobs kn;
+  const ScreenPlan p = plan_search(ctx, B, S, k, row_begin == 0 && n_rows == B, kn, exact_blocks, chr_cum, n_chr);
+  switch (p.path) {
+    case ScreenPath::sym:
+      return screen_sym_path(ctx, kn, p, dXs, B, S, chr_cum, n_chr, k, d_out_idx, d_out_dist);
+    case ScreenPath::exact:
+      return wcx_topk_exact_launch(ctx, dXs, B, S, exact_blocks, row_begin, n_rows, k, d_out_idx, d_out_dist);
+    default:
+      return screen_one_dir_path(ctx, kn, p, dXs, B, S, chr_cum, n_chr, row_begin, n_rows, k, d_out_idx,
+                                 d_out_dist);
   }
-  rc = wcx_timer_begin(ctx, "topk_refine");
-  if (rc) return rc;
-  rc = wcx_refine_launch(ctx, Xr, S, Sp, tab, row_begin, n_rows, searched, sl, cnt_out, flags, perm,
-                         k, d_out_idx, d_out_dist, glob);
-  if (rc) return rc;
-  rc = wcx_timer_end(ctx, "topk_refine");
-  if (rc) return rc;
-  // rows the screen could not finish (none on all data seen) are redone exactly, device-driven:
-  // redo list and its length never leave the device
-  k_collect_redo<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(row_begin, n_rows, searched, flags,
-                                                                   tab, d_redo, d_nredo, ctx->d_stats);
-  k_redo_plan<<<1, 64, 0, st>>>(tab, d_nredo, d_rtile);
-  k_redo_fill<<<(unsigned)((n_rows + NT - 1) / NT), NT, 0, st>>>(row_begin, n_rows, searched, flags, tab,
-                                                                d_nredo, d_rlist);
-  WCX_HIP(hipGetLastError());
-  rc = wcx_topk_exact_redo_launch(ctx, dXs, B, S, d_redo, d_nredo, d_rtile, d_nredo + 1, d_rlist,
-                                  base + o_rscr, row_begin, k, d_out_idx, d_out_dist);
-  if (rc) return rc;
-  return wcx_timer_end(ctx, "topk");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2113,23 +2092,10 @@ int wcx_sym_shard_sweep(wcx_ctx *ctx, const double *dXs, int64_t B, int S, const
                   n_parts);
     return WCX_ERR_UNSUPPORTED;
   }
-  static const int nk_list[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64};
-  int NK = 64;
-  for (int v : nk_list)
-    if (16 * v >= S + 4) { NK = v; break; }
-  ScreenCfg cfg;
-  cfg.nk = NK;
-  cfg.prof = 0;
-  if (NK <= 8) { cfg.ctg = 2; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 3; cfg.ring = 3; }
-  else if (NK <= 32) { cfg.ctg = NK <= 16 ? 2 : 1; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 2; cfg.ring = 2; }
-  else { cfg.ctg = 1; cfg.tt = 1; cfg.wpb = 4; cfg.lb = 1; cfg.ring = 2; }
-  int hw_cus = 256;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
-      hw_cus = prop.multiProcessorCount;
-  }
-  const int slots = hw_cus * (cfg.lb * 4 / cfg.wpb > 0 ? cfg.lb * 4 / cfg.wpb : 1);
+  const Knobs kn;
+  ScreenPlan p = plan_shape(ctx, B, k, default_cfg(screen_nk(S)), kn);
+  p.SF = 16;
+  p.cut_r = 0;
   if (!ctx->sym_state) ctx->sym_state = new SymShardState();
   SymShardState *Z = reinterpret_cast<SymShardState *>(ctx->sym_state);
   Z->valid = false;
@@ -2142,9 +2108,7 @@ int wcx_sym_shard_sweep(wcx_ctx *ctx, const double *dXs, int64_t B, int S, const
     wcx_set_error("row_bounds must run from 0 to B");
     return WCX_ERR_ARG;
   }
-  std::vector<ScreenBlock> none;
-  const int rc = screen_sym_path(ctx, dXs, B, S, chr_cum, n_chr, none, cfg, 16, 0, 1, slots, k, nullptr, nullptr,
-                                 &call);
+  const int rc = screen_sym_path(ctx, kn, p, dXs, B, S, chr_cum, n_chr, k, nullptr, nullptr, &call);
   if (rc) return rc;
   for (int r = 0; r < n_parts; ++r) counts_out[r] = Z->overflow ? -1 : (int64_t)Z->counts[r];
   return WCX_OK;
@@ -2181,44 +2145,20 @@ int wcx_sym_shard_finish(wcx_ctx *ctx, const void *d_recv, int64_t n_recv, int32
   if (n_own <= 0) return wcx_timer_end(ctx, "topk");
   int rc = wcx_timer_begin(ctx, "topk_cut");
   if (rc) return rc;
-  int *cnt = Z->cnt + r0;
-  unsigned int *flags = Z->flags + r0;
-  WCX_HIP(hipMemsetAsync(cnt, 0, (size_t)n_own * 4, st));
+  TopkTail t = Z->tail;
+  t.cnt += r0;
+  t.flags += r0;
+  WCX_HIP(hipMemsetAsync(t.cnt, 0, (size_t)n_own * 4, st));
   // n_recv < 0: some rank's record pool overflowed, the exchange is void -- every row of this rank goes to
   // the exact kernel (flags != 0), like the unsharded path's overflow
-  if (n_recv < 0) WCX_HIP(hipMemsetAsync(flags, 1, (size_t)n_own * 4, st));
+  if (n_recv < 0) WCX_HIP(hipMemsetAsync(t.flags, 1, (size_t)n_own * 4, st));
   if (n_recv > 0)
-    k_rec_regroup<<<2048, NT, 0, st>>>(reinterpret_cast<const uint4 *>(d_recv), n_recv, r0, n_own, Z->sl, cnt, flags,
-                                       Z->cap2);
-  const float gamma = (float)(16 * Z->NK + 12) * 1.1920929e-7f;
-  const unsigned gf = (unsigned)((n_own + 3) / 4 < 65536 ? (n_own + 3) / 4 : 65536);
-  if (Z->cap2 == CAP2)
-    k_sym_final<CAP2 / 64><<<gf, NT, 0, st>>>(Z->info, Z->glob, Z->rowpos + r0, n_own, Z->sl, cnt, flags,
-                                              Z->Dest + r0, Z->k, gamma, CAP, nullptr);
-  else
-    k_sym_final<CAP2_BIG / 64><<<gf, NT, 0, st>>>(Z->info, Z->glob, Z->rowpos + r0, n_own, Z->sl, cnt, flags,
-                                                  Z->Dest + r0, Z->k, gamma, REFINE_MAX, nullptr);
-  WCX_HIP(hipGetLastError());
+    k_rec_regroup<<<2048, NT, 0, st>>>(reinterpret_cast<const uint4 *>(d_recv), n_recv, r0, n_own, t.sl, t.cnt,
+                                       t.flags, t.cap2);
+  rc = sym_final(Z->NK, t.cap2, Z->info, t.glob, Z->rowpos + r0, n_own, t.sl, t.cnt, t.flags, Z->Dest + r0, t.k,
+                 nullptr, st);
+  if (rc) return rc;
   rc = wcx_timer_end(ctx, "topk_cut");
   if (rc) return rc;
-  if (ctx->ev_after_sweep) WCX_HIP(hipEventRecord(ctx->ev_after_sweep, st));
-  rc = wcx_aux_kick(ctx);
-  if (rc) return rc;
-  rc = wcx_timer_begin(ctx, "topk_refine");
-  if (rc) return rc;
-  rc = wcx_refine_launch(ctx, Z->Xr, Z->S, Z->Sp, Z->tab, r0, n_own, Z->searched, Z->sl, cnt, flags, Z->perm,
-                         Z->k, d_out_idx, d_out_dist, Z->glob, Z->cap2);
-  if (rc) return rc;
-  rc = wcx_timer_end(ctx, "topk_refine");
-  if (rc) return rc;
-  k_collect_redo<<<(unsigned)((n_own + NT - 1) / NT), NT, 0, st>>>(r0, n_own, Z->searched, flags, Z->tab, Z->d_redo,
-                                                                  Z->d_nredo, ctx->d_stats);
-  k_redo_plan<<<1, 64, 0, st>>>(Z->tab, Z->d_nredo, Z->d_rtile);
-  k_redo_fill<<<(unsigned)((n_own + NT - 1) / NT), NT, 0, st>>>(r0, n_own, Z->searched, flags, Z->tab, Z->d_nredo,
-                                                               Z->d_rlist);
-  WCX_HIP(hipGetLastError());
-  rc = wcx_topk_exact_redo_launch(ctx, Z->dXs, Z->B, Z->S, Z->d_redo, Z->d_nredo, Z->d_rtile, Z->d_nredo + 1,
-                                  Z->d_rlist, Z->rscr, r0, Z->k, d_out_idx, d_out_dist);
-  if (rc) return rc;
-  return wcx_timer_end(ctx, "topk");
+  return finish_topk(ctx, t, r0, n_own, true, d_out_idx, d_out_dist);
 }
