@@ -248,6 +248,61 @@ def normalize_repeat(test_data, masked_bins_per_chr, masked_bins_per_chr_cum, in
     return results_z, results_r, ref_sizes, m_lr, m_z
 
 
+def ref_rows(masked_bins_per_chr, masked_bins_per_chr_cum, indexes, ct):
+    """For every bin i >= ct, the positions in test_copy that normalize_once's
+    chr_data[index] reads (chr_data = test_copy without bin i's chromosome; a negative index
+    counts from the end of chr_data, as NumPy does): int64 [B - ct][k]."""
+    mb = np.asarray(masked_bins_per_chr, dtype=np.int64)
+    cum = np.asarray(masked_bins_per_chr_cum, dtype=np.int64)
+    B = int(cum[-1])
+    c = np.searchsorted(cum, np.arange(ct, B), side="right")    # chromosome of each bin
+    own, start = mb[c][:, None], (cum - mb)[c][:, None]
+    idx = np.asarray(indexes[ct:], dtype=np.int64)
+    idx = np.where(idx < 0, idx + (B - own), idx)
+    return np.where(idx < start, idx, idx + own)
+
+
+def normalize_repeat_vec(test_data, masked_bins_per_chr, masked_bins_per_chr_cum, indexes,
+                         distances, optimal_cutoff, ct, cp):
+    """normalize_repeat, vectorised over bins: each pass gathers [B - ct][k], drops what
+    normalize_once drops (distance >= cut-off, value < 0 or NaN), then mean, np.std's two-pass
+    deviation and np.median's middle (mean of the two middles for an even count) per row.
+    Pinned to normalize_repeat by tests/test_oracle_normalize_vec.py."""
+    del cp                                        # (ct is the first bin of chromosome cp)
+    x = np.asarray(test_data, dtype=np.float64)
+    g = ref_rows(masked_bins_per_chr, masked_bins_per_chr_cum, indexes, ct)
+    sel = np.asarray(distances[ct:]) < optimal_cutoff
+    own = x[ct:]
+    test_copy = x.copy()
+    with np.errstate(all="ignore"):
+        for p in range(3):
+            v = test_copy[g]
+            keep = sel & (v >= 0)
+            n = keep.sum(axis=1)
+            vk = np.where(keep, v, 0.0)
+            mean = vk.sum(axis=1) / n
+            dev = np.where(keep, v - mean[:, None], 0.0)
+            std = np.sqrt((dev * dev).sum(axis=1) / n)
+            results_z = (own - mean) / std
+            if p < 2:
+                test_copy[ct:][np.abs(results_z) >= Z_MASK] = -1
+        srt = np.sort(np.where(keep, v, np.inf), axis=1)
+        rows = np.arange(len(n))
+        hi = srt[rows, np.minimum(n // 2, srt.shape[1] - 1)]
+        lo = srt[rows, np.maximum(n - 1, 0) // 2]
+        med = np.where(n % 2 == 1, hi, (lo + hi) / 2)
+        med[n == 0] = np.nan
+        results_r = own / med
+        m_lr = _nanmedian_quiet(np.log2(results_r))
+        m_z = _nanmedian_quiet(results_z)
+    return results_z, results_r, n.astype(np.float64), m_lr, m_z
+
+
+def _nanmedian_quiet(a):
+    a = a[~np.isnan(a)]
+    return np.median(a) if a.size else np.nan
+
+
 def normalize(sample, ref, ref_gender, maskrepeats=5):
     """predict_control.py:21-39.  `ref` is a dict / NpzFile with the reference keys."""
     if ref_gender == "A":

@@ -384,6 +384,47 @@ __global__ __launch_bounds__(NT) void k_normalize_mask_lanes(
   }
 }
 
+// z of sample s (= this lane) at bin i from the bin's kept reference values taken directly: two walks over
+// the selected rows of copy[row][NS], the mean, then the squared deviations about it (np.std's order of
+// operations); the count goes to *n_out.  Wave-uniform control flow: every lane walks the same rows.
+__device__ __forceinline__ double direct_z(const double *__restrict__ copy, const int32_t *__restrict__ idx,
+                                           const unsigned long long *__restrict__ sel, int64_t i, int k, int ipl,
+                                           int NS, int s, int64_t cs, int64_t own, int64_t len_cd, double c0,
+                                           double *__restrict__ n_out) {
+  const int lane = wcx::lane_id();
+  double sum = 0.0, ss = 0.0;
+  int ne = 0;
+  for (int walk = 0; walk < 2; ++walk) {
+    const double mean_e = walk ? sum / (double)ne : 0.0;
+    for (int q = 0; q < ipl; ++q) {
+      const int t = q * 64 + lane;
+      int gv = 0;
+      if (t < k) {
+        int64_t c = idx[i * (int64_t)k + t];
+        if (c < 0) c += len_cd;
+        gv = (int)(c < cs ? c : c + own);
+      }
+      const unsigned long long wv = sel[i * ipl + q];
+      unsigned long long w = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(wv >> 32)) << 32) |
+                             (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)wv);
+      if (q == ipl - 1 && (k & 63)) w &= (1ull << (k & 63)) - 1ull;
+      while (w) {
+        const int b = __builtin_ctzll(w);
+        w &= w - 1ull;
+        const int g = __builtin_amdgcn_readlane(gv, b);
+        const double v = copy[(int64_t)g * NS + s];
+        if (v >= 0.0) {                               // predict_tools.py:134
+          if (walk == 0) { sum += v; ne += 1; }
+          else { const double e = v - mean_e; ss += e * e; }
+        }
+      }
+    }
+  }
+  const double dne = (double)ne;
+  *n_out = dne;
+  return (c0 - sum / dne) / sqrt(ss / dne);
+}
+
 // Pass 1 of a BATCH without a second sweep of the gathers.  Pass 0 (k_normalize_mask_lanes) left every
 // (bin, sample)'s sums S1, S2 about c0 and count n over its selected, kept reference bins, and per (bin,
 // 64-sample tile) the WORD of samples it masked (|z| >= 3).  Pass 1's set is pass 0's minus the reference
@@ -416,6 +457,7 @@ __global__ __launch_bounds__(NT) void k_normalize_mask_incr(
     const int64_t own = ce - cs;
     const int64_t len_cd = B - own;
     const double c0 = xT[i * NS + s];
+    bool small = false;
     if (zT) {
       // Statistics of the last pass for a bin with FEW selected reference bins (its distances mostly beyond
       // the cut-off: one or two references are common among them): the updated sums carry the rounding of
@@ -430,45 +472,21 @@ __global__ __launch_bounds__(NT) void k_normalize_mask_incr(
         nsel += __popcll(w);
       }
       nsel = __builtin_amdgcn_readfirstlane(nsel);
-      if (nsel <= 32) {
-        double sum = 0.0, ss = 0.0;
-        int ne = 0;
-        for (int walk = 0; walk < 2; ++walk) {
-          const double mean_e = walk ? sum / (double)ne : 0.0;
-          for (int q = 0; q < ipl; ++q) {
-            const int t = q * 64 + lane;
-            int gv = 0;
-            if (t < k) {
-              int64_t c = idx[i * (int64_t)k + t];
-              if (c < 0) c += len_cd;
-              gv = (int)(c < cs ? c : c + own);
-            }
-            const unsigned long long wv = sel[i * ipl + q];
-            unsigned long long w = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(wv >> 32)) << 32) |
-                                   (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)wv);
-            if (q == ipl - 1 && (k & 63)) w &= (1ull << (k & 63)) - 1ull;
-            while (w) {
-              const int b = __builtin_ctzll(w);
-              w &= w - 1ull;
-              const int g = __builtin_amdgcn_readlane(gv, b);
-              const double v = copy_out[(int64_t)g * NS + s];
-              if (v >= 0.0) {                         // predict_tools.py:134
-                if (walk == 0) { sum += v; ne += 1; }
-                else { const double e = v - mean_e; ss += e * e; }
-              }
-            }
-          }
-        }
-        const double dne = (double)ne;
-        const double mean_e = sum / dne;
-        zT[i * NS + s] = (c0 - mean_e) / sqrt(ss / dne);
-        nT[i * NS + s] = dne;
-        continue;
-      }
+      small = nsel <= 32;
     }
-    double S1 = st_S1[i * NS + s], S2 = st_S2[i * NS + s];
-    int n = st_n[i * NS + s];
-    for (int q = 0; q < ipl; ++q) {
+    double S1 = 0.0, S2 = 0.0;
+    int n = 0, s2_tag = 0;
+    // st_n: the count; from pass 1's write-back on its upper half (bits 16..) holds the exponent + 1100 of pass
+    // 0's sum of squares -- the largest the sums held (bins only leave them), so the scale of their rounding
+    if (!small) {
+      S1 = st_S1[i * NS + s];
+      S2 = st_S2[i * NS + s];
+      const int n_tag = st_n[i * NS + s];
+      n = n_tag & 0xffff;
+      s2_tag = n_tag >> 16;
+      if (s2_tag == 0 && S2 > 0.0 && S2 <= 0x1.fffffffffffffp+1023) { frexp(S2, &s2_tag); s2_tag += 1100; }
+    }
+    for (int q = 0; q < (small ? 0 : ipl); ++q) {
       const int t = q * 64 + lane;
       int gv = 0;
       bool selq = false;
@@ -509,14 +527,31 @@ __global__ __launch_bounds__(NT) void k_normalize_mask_incr(
         }
       }
     }
+    // every reference bin taken away again: what is left of the sums is rounding, the set is empty (np.mean
+    // of it: nan, never +-inf -- a z of +-inf would mask the bin)
+    if (n == 0) { S1 = 0.0; S2 = 0.0; }
     const double dn = (double)n;
     const double mean = c0 + S1 / dn;
     const double var = (S2 - S1 * (S1 / dn)) / dn;
     const double sd = sqrt(var > 0.0 ? var : 0.0);
-    const double z = (c0 - mean) / sd;                // predict_tools.py:136
+    double z = (c0 - mean) / sd;                      // predict_tools.py:136
     if (zT) {                                         // statistics of the last pass
+      // The sums' rounding is ~ n ulp of the largest S2 / n they held (pass 0's; S2 / n = var (1 + z^2) about c0):
+      // var keeps ~9 digits only while it is above ~2^-12 of that.  Below -- a bin's own value far off its set
+      // (|z| > ~64), a set that lost its heavy values to the mask, a set of identical values (np.std 0 exactly,
+      // z = +-inf, where the sums leave dust) -- the set is walked directly, as for small sets above.  (Uniform:
+      // the wave walks if any of its samples needs it.)
+      const double S2_hi = s2_tag ? ldexp(1.0, s2_tag - 1100) : 0.0;
+      const bool direct = small || var < S2_hi / dn * 0x1p-12;   // (false for nan: c0 or the set empty; and for
+                                                                 //  S2 = 0 all along: padding samples, a set = c0)
+      double ne = dn;
+      if (__ballot(direct)) {
+        double ne_d;
+        const double zd = direct_z(copy_out, idx, sel, i, k, ipl, NS, s, cs, own, len_cd, c0, &ne_d);
+        if (direct) { z = zd; ne = ne_d; }
+      }
       zT[i * NS + s] = z;
-      nT[i * NS + s] = dn;
+      nT[i * NS + s] = ne;
       continue;
     }
     const bool was = ((st_was ? st_was : st_mask)[i * n_tiles + blockIdx.y] >> lane) & 1ull;
@@ -524,7 +559,7 @@ __global__ __launch_bounds__(NT) void k_normalize_mask_incr(
     if (st_mask_new) {
       st_S1[i * NS + s] = S1;
       st_S2[i * NS + s] = S2;
-      st_n[i * NS + s] = n;
+      st_n[i * NS + s] = n | (s2_tag << 16);
       const unsigned long long m = __ballot(!was && fabs(z) >= Z_MASK && c0 >= 0.0);
       if (lane == 0) st_mask_new[i * n_tiles + blockIdx.y] = m;
     }
